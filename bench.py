@@ -4,9 +4,13 @@ Headline benchmark: matrix-free H|psi> for the random-field Heisenberg chain
 (reference benchmarking/benchmark.py 'MBL' Hamiltonian, `--shell --mult`),
 Full space, complex128, on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--L L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--L L] [--full] [--dump-outputs DIR]
 
-A "step" is one multiply y = H x with x, y resident in HBM.  N=1: L=30 (2^30
+A "step" is one multiply y = H x with x, y resident in HBM.  A plain run sets up, warms up, times the K steps and
+prints the line; everything else the line can carry -- the Krylov phases and SYK / kagome solves of `secondary`, the
+CPU baseline, and on N > 1 the multiply split into phases for both exchange schedules and config 5 -- runs only with
+`--full`.  `--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of rows of y, see
+`dump_outputs`) as .npy files, so that two builds can be compared output for output.  N=1: L=30 (2^30
 amplitudes, 16 GiB per vector; BASELINE.json configs[2]).  N=2, 4: the state is
 row-block partitioned, L = 30 + log2(N) so every GPU keeps 2^30 amplitudes
 (weak scaling); N=8: L=34, the size of BASELINE.json configs[3] (2^31 amplitudes,
@@ -14,7 +18,7 @@ row-block partitioned, L = 30 + log2(N) so every GPU keeps 2^30 amplitudes
 all-to-all between two layouts from 4 on -- DESIGN.md section 6) travels over
 RCCL while the rank-local masks run.  Prints ONE JSON line on rank 0.
 
-Every N > 1 line also carries, under `multi_gpu`, the multiply split three ways for BOTH schedules of the exchange -- the
+With `--full`, every N > 1 line also carries, under `multi_gpu`, the multiply split three ways for BOTH schedules of the exchange -- the
 native one (dnm_mat_mult_partitioned: the library's own RCCL communicator and stream; the default on RCCL) and the host
 one (torch.distributed) --: the whole multiply, its messages alone (with the rate the busiest link reached,
 `link_GBs_measured`, next to the assumed one the prediction uses), its kernels alone, and how much of the exchange the
@@ -663,7 +667,7 @@ def dry_run(args, world, rank, wd=None):
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     # config 5's exchange at a toy size: every rank's column window from its host-only handle, the ranges travel over gloo
     sec = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         if wd:
             wd.phase("dry run: config 5's window exchange")
         try:
@@ -1018,6 +1022,36 @@ def config5(wd, world, rank, Lk=None, tol=1e-8):
     return out
 
 
+DUMP_ROWS = 1 << 20         # rows of y that --dump-outputs writes: 16 MiB of values + 8 MiB of row numbers
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, y, dim, world, rank):
+    """`--dump-outputs`: what the timed path hands its caller is y = H x.  Its rows at a fixed, seeded sample (every row
+    when dim <= DUMP_ROWS), in increasing order, go to out_dir/y.npy as float64 [re, im] pairs and the row numbers to
+    out_dir/y_rows.npy (float64: exact below 2^53).  Collective on several ranks: each fills in the rows it owns."""
+    import numpy as np
+    import torch
+    n = min(dim, DUMP_ROWS)
+    if n == dim:
+        rows = np.arange(dim, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(dim, size=n, replace=False))
+    lo, hi = y.getOwnershipRange()
+    mine = np.nonzero((rows >= lo) & (rows < hi))[0]
+    dev = y.array.device
+    vals = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+    pos = y.positions(torch.from_numpy(rows[mine] - lo).to(dev))           # local rows -> places in y's layout
+    vals[torch.from_numpy(mine).to(dev)] = torch.view_as_real(y.array[pos])
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(vals)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "y.npy"), vals.cpu().numpy())
+        np.save(os.path.join(out_dir, "y_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1025,8 +1059,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--L", type=int, default=0)
     ap.add_argument("--model", default="mbl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the evolve / eigsolve phases of the line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: secondary phases, CPU baseline, the multi-GPU "
+                         "phase split of both schedules, config 5")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a seeded sample of rows of the last timed step's y to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the evolve / eigsolve phases of the line")
     ap.add_argument("--watchdog", type=int, default=900, help="seconds a phase may take before the rank gives up (0: off)")
     ap.add_argument("--timeout", type=int, default=3600, help="time limit of a self-launched multi-rank run (0: none)")
     ap.add_argument("--no-probe", action="store_true", help="several GPUs: skip the first-contact probe of the native schedule")
@@ -1034,6 +1073,8 @@ def main():
     ap.add_argument("--probe-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--config5", default=None, help="L,k of the SpinConserve eigsolve of a multi-GPU line (default by rank count)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.probe_child:
         sys.exit(probe_child(args))
@@ -1178,6 +1219,9 @@ def main():
     # sanity: the timed multiply produced a finite vector of the expected size
     ynorm = y.norm()
     assert math.isfinite(ynorm) and ynorm > 0
+    if args.dump_outputs:
+        wd.phase("dump outputs")
+        dump_outputs(args.dump_outputs, y, dim, world, rank)
     summary = mat.exchange_summary()
     if world > 1:       # the heaviest rank (partner blocks differ from rank to rank: rank 0 needs the least)
         t = torch.tensor([summary["bytes_in"], summary["bytes_out"], summary["busiest_link_bytes"], summary["peers"]],
@@ -1261,7 +1305,7 @@ def main():
         }
         wd.partial = out
 
-    if world > 1:
+    if world > 1 and args.full:
         # the multiply split three ways, for both schedules of the exchange
         mg = {"default_schedule": "native" if native_default else "host", "first_contact_probe": probe,
               "xgmi_link_GBs_assumed": XGMI_LINK_GBS, "schedules": {}}
@@ -1304,7 +1348,7 @@ def main():
                                                     "DNM_NATIVE_COMM=0" if os.environ.get("DNM_NATIVE_COMM", "") == "0" else
                                                     "no RCCL transport (gloo-staged ranks)")
 
-    if not args.no_secondary and ((n_gpus == 1 and L == 30) or n_gpus > 1):
+    if args.full and not args.no_secondary and ((n_gpus == 1 and L == 30) or n_gpus > 1):
         # the headline's vectors and operator go first: the solvers size their work space to the free memory
         if mat is not None:
             mat.destroy()
@@ -1332,7 +1376,7 @@ def main():
             if not out["secondary_ok"]:
                 print("[bench] secondary phases with failed checks or errors: %s" % (bad or sec.get("error")), file=sys.stderr)
     if rank == 0:
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             wd.phase("cpu baseline")
             try:
                 out["cpu_baseline"] = cpu_baseline()

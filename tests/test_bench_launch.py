@@ -22,7 +22,7 @@ def test_bench_spawns_its_ranks(n):
         pytest.skip("dry-run flow is the no-GPU path")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2",
-                        "--warmup", "1", "--L", "16"], capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--L", "16", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -180,3 +180,42 @@ def test_probe_child_environment():
     src = inspect.getsource(bench.first_contact_probe)
     assert "TORCHELASTIC_" in src and "PROBE_PORT_OFFSET" in src and 'env["DNM_NATIVE_COMM"]' in src
     assert "p.kill()" in src and "pkill" not in src          # the exact child, never a pattern
+
+
+@pytest.mark.gpu
+@pytest.mark.default_layout
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain one-GPU run times its steps and nothing else (no `secondary`, no `cpu_baseline`: those need --full), and
+    --dump-outputs writes the last step's y at the seeded sample of rows: the oracle's H x at those rows, x being the
+    bench's own seeded input."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from dynamite_amd import models, backend, msc_tools
+    from dynamite_amd.subspaces import Full
+    from oracle import oracle as orc
+    L, steps = 21, 3                    # 2^21 rows > bench.DUMP_ROWS: the sampled form
+    p = _run_bench(["--steps", str(steps), "--warmup", "1", "--L", str(L), "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["value"] > 0 and out["config"]["L"] == L
+    assert "secondary" not in out and "cpu_baseline" not in out and "multi_gpu" not in out
+    y, rows = np.load(str(tmp_path / "y.npy")), np.load(str(tmp_path / "y_rows.npy"))
+    assert y.dtype == np.float64 and y.shape == (bench.DUMP_ROWS, 2) and rows.shape == (bench.DUMP_ROWS,)
+    r = rows.astype(np.int64)
+    assert (r == rows).all() and (np.diff(r) > 0).all() and 0 <= r[0] and r[-1] < 1 << L
+    H = models.mbl(L)
+    H.establish_L()
+    H.reduce_msc()
+    masks, offs = msc_tools.get_mask_offsets(H.msc)
+    sub = Full(L=L)
+    mat = backend.build_mat(masks, offs, H.msc['signs'], H.msc['coeffs'], sub._to_c(), sub._to_c())
+    x, _ = mat.createVecs()
+    x.set_random(0)
+    x.normalize()
+    ref = orc.matvec(orc.Msc(masks, offs, H.msc['signs'], H.msc['coeffs']), orc.full(L), orc.full(L), x.to_numpy(),
+                     nthreads=8)
+    mat.destroy()
+    assert np.max(np.abs(y[:, 0] + 1j * y[:, 1] - ref[r])) < 1e-12

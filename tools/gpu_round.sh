@@ -15,4 +15,4 @@ timeout 300 python tools/sweep.py 26 2>&1 | tee $OUT/sweep_L26.txt
 echo "== sweep L=30" | tee -a $OUT/log.txt
 timeout 600 python tools/sweep.py 30 2>&1 | tee $OUT/sweep_L30.txt
 echo "== bench" | tee -a $OUT/log.txt
-timeout 600 python bench.py --steps 10 --warmup 2 2> $OUT/bench_stderr.txt | tee $OUT/bench.json
+timeout 600 python bench.py --full --steps 10 --warmup 2 2> $OUT/bench_stderr.txt | tee $OUT/bench.json
