@@ -33,6 +33,7 @@ def _dist():
 
 
 _NATIVE_COMM = None
+_NATIVE_GEN = 0         # generation of the communicator: counts releases, so that an operator knows a stale binding
 
 
 def native_comm():
@@ -58,10 +59,12 @@ def native_comm():
 
 def release_native_comm():
     """Destroy the library's communicator (ncclCommDestroy, the exchange stream): collective in spirit -- every rank
-    calls it, after the last operator that used it has been destroyed and before the process group goes."""
-    global _NATIVE_COMM
+    calls it, after the last operator that used it has been destroyed and before the process group goes.  An operator
+    still bound to it refuses the native schedule from then on and forgets nothing when destroyed."""
+    global _NATIVE_COMM, _NATIVE_GEN
     if _NATIVE_COMM is not None:
         h, _NATIVE_COMM = _NATIVE_COMM, None
+        _NATIVE_GEN += 1
         _lib.check(_lib.lib().dnm_comm_destroy(h))
 
 
@@ -742,25 +745,25 @@ class ShellMat:
         self.perm_right = site_perm_of(right_c) if lr.value >= 256 else None
         self.sends, self.recvs = exchange_plan(handle)
         self.partners = sorted({r[0] for r in self.recvs})
-        self._recv = {}
         r0, ml = C.c_int64(), C.c_int64()
         _lib.check(_lib.lib().dnm_mat_ownership(handle, C.byref(r0), C.byref(ml)))
         self.row0 = r0.value
-        self._windows = None      # partitioned SpinConserve: every rank's column window
-        self._needs = None        # ... and the ranges of it each rank really reads
-        self._window_buf = None
-        self._tr = None           # transposed exchange (set_transposed): (lo handle, hi handle, pieces, own, cnt)
-        self._tr_bufs = None
-        self._tr_pipe = False     # layout-B pass and both all-to-alls run sub-piece by sub-piece (_mult_transposed_pipelined)
-        self._splits = None       # window multiply in a local and a remote part (dnm_mat_window_split)
-        self._row_ranges = None   # ... or by rows: (ranges that read only the rank's own block, the others)
         self._msc = None          # (masks, mask_offsets, signs, coeffs, left subspace dict, right subspace dict): selfcheck
         self._check_pending = False
-        # the partitioned multiply as one native call (dnm_mat_mult_partitioned: exchange on the library's own RCCL
-        # communicator and stream) instead of the schedules below over torch.distributed -- the default on RCCL
-        # transports (native_transport()); the transposed exchange too (set_native_transposed)
-        self._native = None
-        self._native_tr = False   # transposed exchange split and scheduled inside the library (set_native_transposed)
+        # The schedule of the partitioned multiply, decided on first use (_resolve), and what each one keeps:
+        self._schedule = None     # 'local', 'partner', 'window', 'transpose' (host) or 'native'
+        self._scheme = None       # ... and the form of its exchange, as exchange_summary names it
+        self._recv = None         # partner: the receive buffers, one per entry of recvs (recv_buffers)
+        self._windows = None      # window: every rank's column window and block (_owned) ...
+        self._needs = None        # ... the ranges of its window each rank really reads ...
+        self._window_buf = None   # ... this rank's window ...
+        self._splits = None       # ... multiplied in a local and a remote part (dnm_mat_window_split) ...
+        self._row_ranges = None   # ... or by rows: (ranges that read only the rank's own block, the others)
+        self._tr = None           # transpose: (lo handle, hi handle, pieces, own, cnt) of the host's split (set_transposed)
+        self._tr_bufs = None      # ... the state and the result in layout B ...
+        self._tr_pipe = False     # ... run sub-piece by sub-piece (_mult_transposed_pipelined)
+        self._native_tr = None    # native: the same of the split inside the library (set_native_transposed) ...
+        self._comm = None         # ... the communicator and its generation: (dnm_comm handle, _NATIVE_GEN)
 
     @property
     def handle(self):
@@ -828,9 +831,7 @@ class ShellMat:
         return buf.value.decode()
 
     def mult(self, x, y):
-        """y = A x (MatMult).  Partitioned: the partners' blocks travel over RCCL
-        send/recv while the rank-local masks are applied; the off-rank masks
-        follow once their block has arrived."""
+        """y = A x (MatMult), through the operator's schedule (``_resolve``)."""
         L = _lib.lib()
         if x.array.data_ptr() == y.array.data_ptr():
             raise ValueError('x and y must be different vectors')
@@ -838,40 +839,32 @@ class ShellMat:
                 and self._mult_converted(x, y):
             return
         self.check_layout(x, y)
-        if self._tr is not None or self._native_tr:
-            if self._native_tr:
-                # split and schedule inside the library (dnm_mat_set_exchange, csrc/comm.cpp)
-                if self._native is None:
-                    self._native = native_comm()
-                _lib.check(L.dnm_mat_mult_partitioned(self.handle, self._native, x.ptr, y.ptr, _stream()))
-            else:
-                self._mult_transposed(x, y)
-            if self._check_pending:
-                # The transposed exchange is the scheme with the most asynchronous traffic (buffers shared between
-                # the RCCL stream and the compute stream, batched returns): its first result on a transport is
-                # checked against rows recomputed from the MSC definition before anything is built on it.
-                self._check_pending = False
-                err, scale = self.selfcheck(x, y)
-                if not err <= 1e-9 * max(scale, 1e-300):
-                    raise ExchangeCheckError('transposed exchange: sampled rows of the first multiply are off by %.3e '
-                                             '(scale %.3e); build the operator with exchange="partner"' % (err, scale))
-            return
-        if self._native is None and self.nranks > 1 and self._native_applies(x):
-            self._native = native_comm()
-        if self._native is not None and self.nranks > 1:
-            _lib.check(L.dnm_mat_mult_partitioned(self.handle, self._native, x.ptr, y.ptr, _stream()))
-            return
-        if self.nranks > 1 and not self.partners and self._is_windowed():
+        s = self._resolve(x.array.is_cuda)
+        if s == 'window':
             return self._mult_window(x, y)
-        if not self.recvs and not self.sends:
+        if s == 'local':
             _lib.check(L.dnm_mat_mult(self.handle, x.ptr, y.ptr, _stream()))
-            return
-        import torch
-        bufs = []
-        for i, (p, off, cnt) in enumerate(self.recvs):
-            if i not in self._recv:
-                self._recv[i] = torch.empty(cnt, dtype=x.array.dtype, device=x.array.device)
-            bufs.append(self._recv[i])
+        elif s == 'partner':
+            self._mult_partner(x, y)
+        elif s == 'transpose':
+            self._mult_transposed(x, y)
+        else:
+            # split and schedule inside the library (dnm_mat_set_exchange, csrc/comm.cpp)
+            _lib.check(L.dnm_mat_mult_partitioned(self.handle, self._live_comm(), x.ptr, y.ptr, _stream()))
+        if self._check_pending:
+            # The transposed exchange is the scheme with the most asynchronous traffic (buffers shared between
+            # the RCCL stream and the compute stream, batched returns): its first result on a transport is
+            # checked against rows recomputed from the MSC definition before anything is built on it.
+            self._check_pending = False
+            err, scale = self.selfcheck(x, y)
+            if not err <= 1e-9 * max(scale, 1e-300):
+                raise ExchangeCheckError('transposed exchange: sampled rows of the first multiply are off by %.3e '
+                                         '(scale %.3e); build the operator with exchange="partner"' % (err, scale))
+
+    def _mult_partner(self, x, y):
+        """The partners' blocks travel while the rank-local masks are applied, the others follow as blocks arrive."""
+        L = _lib.lib()
+        bufs = self.recv_buffers(x.array)
         reqs = post_exchange(x.array, self.sends, self.recvs, bufs)     # runs on RCCL's stream
         _lib.check(L.dnm_mat_mult_local(self.handle, x.ptr, y.ptr, _stream()))   # overlaps
         # one request per posted operation (sends first, then the receives in order): wait per received block and
@@ -890,6 +883,71 @@ class ShellMat:
                 r.wait()
             for i in range(nr):
                 _lib.check(L.dnm_mat_mult_remote(self.handle, i, C.c_void_p(bufs[i].data_ptr()), y.ptr, _stream()))
+
+    def recv_buffers(self, like):
+        """The partner blocks' receive buffers, one per entry of ``recvs``; ``like``: a local vector (dtype / device)."""
+        import torch
+        if self._recv is None:
+            self._recv = [torch.empty(cnt, dtype=like.dtype, device=like.device) for _, _, cnt in self.recvs]
+        return self._recv
+
+    def _resolve(self, on_device=True, hooks=False):
+        """The schedule of the partitioned multiply, decided on first use and kept: one rank -> 'local'; the host's
+        transposed split -> 'transpose'; the library's split, or native_transport() with vectors in device memory ->
+        'native'; no partners and an untiled plan (columns gathered into a window from the neighbours) -> 'window';
+        sends or receives -> 'partner'; else 'local'.  ``hooks``: whether the solvers' hooks go native instead -- on an
+        RCCL transport unless the schedule is the host's transposed exchange; that makes a multi-rank schedule native."""
+        if self._schedule is None:
+            windowed = self.nranks > 1 and not self.partners and 'tiled=1' not in self.describe()
+            self._scheme = 'transpose' if self._tr or self._native_tr else 'window' if windowed else 'partner'
+            self._schedule = ('local' if self.nranks == 1 else 'transpose' if self._tr else
+                              'native' if self._native_tr or (on_device and native_transport()) else
+                              'window' if windowed else 'partner' if self.recvs or self.sends else 'local')
+        if hooks:
+            native = self._schedule != 'transpose' and native_transport()
+            if native:
+                self.bind_native()
+            return native
+        return self._schedule
+
+    @property
+    def schedule(self):
+        """'local', 'partner', 'window', 'transpose' or 'native' (``_resolve``); None before the first use."""
+        return self._schedule
+
+    # the communicator bound for the native schedule, None before (the attribute's older readers); assigning binds it
+    _native = property(lambda self: self._comm and self._comm[0], lambda self, comm: self.bind_native(comm))
+
+    @property
+    def transpose_pipelined(self):
+        """Whether the host's transposed exchange runs sub-piece by sub-piece (``_mult_transposed_pipelined``)."""
+        return self._tr_pipe
+
+    def bind_native(self, comm=None):
+        """Bind the library's communicator -- ``native_comm()``; ``comm``: the same after dnm_comm_loopback has made it
+        stand for a rank of many (tests) -- and make a multi-rank operator's schedule native."""
+        if self._resolve() == 'transpose' or (comm is not None and comm.value != getattr(_NATIVE_COMM, 'value', None)):
+            raise ValueError('bind_native: the operator runs the host\'s transposed exchange, or comm is not native_comm()')
+        self._live_comm()
+        if self.nranks > 1:
+            self._schedule = 'native'
+
+    def _live_comm(self):
+        """The communicator of the native schedule, bound on first use; refused once released."""
+        if self._comm is None:
+            self._comm = (native_comm(), _NATIVE_GEN)
+        if self._comm[1] != _NATIVE_GEN:
+            raise RuntimeError('the communicator this operator was bound to is gone (release_native_comm): rebuild it')
+        return self._comm[0]
+
+    def native_hooks(self):
+        """The solvers' hooks on the library's communicator (dnm_comm_hooks: multiply and reductions of every solver
+        step stay native) if ``_resolve`` says so; None: the caller makes its own over torch.distributed."""
+        if not self._resolve(hooks=True):
+            return None
+        h = _lib.Hooks()
+        _lib.check(_lib.lib().dnm_comm_hooks(self._live_comm(), self.handle, _stream(), C.byref(h)))
+        return h
 
     def vec_in(self, v):
         """``v`` as an input vector in this matrix's layout: itself, or a copy made through the reference order (a
@@ -910,12 +968,6 @@ class ShellMat:
         if not (v.internal and self.swz_left >= 256 and self.nranks == 1):
             return v
         return Vec(v.size, swz=self.swz_left, sub_c=self._keep[0])
-
-    def _native_applies(self, x):
-        """The native schedule moves device memory over RCCL: every partition takes it (round 6: also window partitions whose
-        right vectors are stored swizzled -- the library straightens the block before it travels); the host schedules
-        remain for the gloo-staged transport of the CPU / one-GPU tests."""
-        return native_transport() and x.array.is_cuda
 
     def check_layout(self, x, y):
         """Raise unless the vectors are laid out as this matrix expects them (x: right subspace, y: left).  Every
@@ -1072,20 +1124,13 @@ class ShellMat:
     def set_native_transposed(self):
         """The transposed exchange with the split and the schedule inside the library (dnm_mat_set_exchange +
         dnm_mat_mult_partitioned): the default on RCCL transports (config.native_comm).  Returns whether the operator splits."""
-        chosen = C.c_int()
+        chosen, lo, hi, f = C.c_int(), C.c_void_p(), C.c_void_p(), C.c_int()
         _lib.check(_lib.lib().dnm_mat_set_exchange(self.handle, _lib.EXCHANGE_TRANSPOSE, C.byref(chosen)))
-        self._native_tr = chosen.value == _lib.EXCHANGE_TRANSPOSE
-        return self._native_tr
-
-    def _transposed_parts(self):
-        """(lo handle, hi handle, pieces, own, cnt) of whichever side holds the split"""
-        if self._tr is not None:
-            return self._tr
-        lo, hi, f = C.c_void_p(), C.c_void_p(), C.c_int()
-        _lib.check(_lib.lib().dnm_mat_exchange_parts(self.handle, C.byref(lo), C.byref(hi), C.byref(f)))
-        p = self.nranks.bit_length() - 1
-        n = (self.n_local - 1).bit_length()
-        return (lo, hi) + transpose_pieces(n, p, f.value, self.rank)
+        if chosen.value == _lib.EXCHANGE_TRANSPOSE:
+            _lib.check(_lib.lib().dnm_mat_exchange_parts(self.handle, C.byref(lo), C.byref(hi), C.byref(f)))
+            n = (self.n_local - 1).bit_length()
+            self._native_tr = (lo, hi) + transpose_pieces(n, self.nranks.bit_length() - 1, f.value, self.rank)
+        return self._native_tr is not None
 
     def launches_per_mult(self):
         """Kernel launches of one multiply on this rank (rank-local passes, partner passes / the pass in the
@@ -1094,39 +1139,33 @@ class ShellMat:
             nl = C.c_int()
             _lib.check(_lib.lib().dnm_mat_plan_launches(h, C.byref(nl)))
             return nl.value
-        if self._tr is not None or self._native_tr:
-            tr = self._transposed_parts()
-            return count(tr[0]) + count(tr[1]) * (self.TR_SUB if (self._tr_pipe or self._native_tr) else 1) + 1
+        s = self._resolve()
+        if self._scheme == 'transpose':
+            tr = self._tr or self._native_tr
+            return count(tr[0]) + count(tr[1]) * (self.TR_SUB if (self._tr_pipe or s == 'native') else 1) + 1
         return count(self.handle) + len(self.recvs)
 
     def exchange_summary(self):
         """What one multiply moves between ranks: bytes received, sent, peers, and the bytes on the busiest
         link (peer) -- for the link-bound estimate of bench.py.  On a window partition the first call sets the
         windows up, which is collective: call it on every rank."""
-        if self._tr is not None or self._native_tr:
-            tr = self._transposed_parts()
-            pieces, cnt = tr[2], tr[4]
-            per_peer = {}
-            for q, _, c in pieces:
-                per_peer[q] = per_peer.get(q, 0) + 2 * 16 * c        # state out and result back
-            tot = sum(per_peer.values())
-            return {'scheme': 'transpose', 'bytes_in': tot, 'bytes_out': tot, 'peers': len(per_peer),
-                    'busiest_link_bytes': max(per_peer.values()) if per_peer else 0}
-        per_peer = {}
-        for q, _, c in self.recvs:
-            per_peer[q] = per_peer.get(q, 0) + 16 * c
-        if self.nranks > 1 and not self.partners and self._is_windowed():
+        self._resolve()
+        extra = {}
+        if self._scheme == 'transpose':
+            rcv = [(q, 2 * c) for q, _, c in (self._tr or self._native_tr)[2]]        # state out and result back
+            out = sum(c for _, c in rcv)
+        elif self._scheme == 'window':
             self._setup_windows()
             rcv, snd = window_exchange_ops(self._owned, self._windows, self.rank, self._needs)
-            for q, lo, hi in rcv:
-                per_peer[q] = per_peer.get(q, 0) + 16 * (hi - lo)
-            return {'scheme': 'window', 'bytes_in': sum(per_peer.values()),
-                    'bytes_out': sum(16 * (hi - lo) for _, lo, hi in snd), 'peers': len(per_peer),
-                    'busiest_link_bytes': max(per_peer.values()) if per_peer else 0,
-                    'window_bytes': 16 * (self._windows[self.rank][1] - self._windows[self.rank][0] + 1)}
-        return {'scheme': 'window' if (self.nranks > 1 and not self.partners and self._is_windowed()) else 'partner',
-                'bytes_in': sum(per_peer.values()), 'bytes_out': sum(16 * c for _, _, c in self.sends),
-                'peers': len(per_peer), 'busiest_link_bytes': max(per_peer.values()) if per_peer else 0}
+            rcv, out = [(q, hi - lo) for q, lo, hi in rcv], sum(hi - lo for _, lo, hi in snd)
+            extra = {'window_bytes': 16 * (self._windows[self.rank][1] - self._windows[self.rank][0] + 1)}
+        else:
+            rcv, out = [(q, c) for q, _, c in self.recvs], sum(c for _, _, c in self.sends)
+        per_peer = {}
+        for q, c in rcv:
+            per_peer[q] = per_peer.get(q, 0) + 16 * c
+        return {'scheme': self._scheme, 'bytes_in': sum(per_peer.values()), 'bytes_out': 16 * out,
+                'peers': len(per_peer), 'busiest_link_bytes': max(per_peer.values(), default=0), **extra}
 
     def _transpose_buffers(self, like):
         import torch
@@ -1241,83 +1280,75 @@ class ShellMat:
 
     TR_SUB = 4     # parts a piece of the returning all-to-all travels in (_mult_transposed)
 
-    def _native_in_use(self, x):
-        """Whether ``mult`` runs this operator through dnm_mat_mult_partitioned (binds the communicator on first use)."""
-        if self.nranks == 1:
-            return False
-        if self._native is None and (self._native_tr or (self._tr is None and self._native_applies(x))):
-            self._native = native_comm()
-        return self._native is not None and (self._native_tr or self._tr is None)
+    def _native_in_use(self, x):       # (bench.py)
+        return self._resolve(x.array.is_cuda) == 'native'
 
     def _native_phase(self, x, y, phase):
-        L = _lib.lib()
-        _lib.check(L.dnm_comm_set_phase(self._native, phase))
+        L, comm = _lib.lib(), self._live_comm()
+        _lib.check(L.dnm_comm_set_phase(comm, phase))
         try:
-            _lib.check(L.dnm_mat_mult_partitioned(self.handle, self._native, x.ptr, y.ptr, _stream()))
+            _lib.check(L.dnm_mat_mult_partitioned(self.handle, comm, x.ptr, y.ptr, _stream()))
         finally:
-            _lib.check(L.dnm_comm_set_phase(self._native, _lib.PHASE_ALL))
+            _lib.check(L.dnm_comm_set_phase(comm, _lib.PHASE_ALL))
 
     def compute_only(self, x, y):
         """The kernels of ONE multiply with nothing on the links (receive buffers / the window / the redistributed state
         hold whatever the last multiply left there): the rank's compute time, for bench.py's split of a partitioned
         multiply into exchange, compute and what the schedule hides.  ``y`` does not hold A x afterwards."""
         L = _lib.lib()
-        if self.nranks == 1:
-            _lib.check(L.dnm_mat_mult(self.handle, x.ptr, y.ptr, _stream()))
-            return
-        if self._native_in_use(x):
-            return self._native_phase(x, y, _lib.PHASE_COMPUTE)
+        s = self._resolve(x.array.is_cuda)
         vp = lambda t: C.c_void_p(t.data_ptr())
-        if self._tr is not None:
+        if s == 'local':
+            _lib.check(L.dnm_mat_mult(self.handle, x.ptr, y.ptr, _stream()))
+        elif s == 'native':
+            self._native_phase(x, y, _lib.PHASE_COMPUTE)
+        elif s == 'transpose':
             lo, hi, pieces, own, cnt = self._tr
             xb, wb = self._transpose_buffers(x.array)
             _lib.check(L.dnm_mat_mult_local(lo, x.ptr, y.ptr, _stream()))
             _lib.check(L.dnm_mat_mult_local(hi, vp(xb), vp(wb), _stream()))
             _lib.check(L.dnm_vec_axpby(y.ptr, vp(wb), self.n_local, 1.0, 0.0, 1.0, 0.0, _stream()))
-        elif not self.partners and self._is_windowed():
-            self._setup_windows()
+        elif s == 'window':
             self.prepare_exchange(x.array)
             w0, wb = self._windows[self.rank][0], self._window_buf
-            if self._window_splits():
+            if self._splits:
                 _lib.check(L.dnm_mat_mult_window_local(self.handle, x.ptr, y.ptr, _stream()))
                 _lib.check(L.dnm_mat_mult_window_remote(self.handle, vp(wb), w0, wb.numel(), y.ptr, _stream()))
             else:
                 _lib.check(L.dnm_mat_mult_window(self.handle, vp(wb), w0, wb.numel(), y.ptr, _stream()))
         else:
-            self.prepare_exchange(x.array)
             _lib.check(L.dnm_mat_mult_local(self.handle, x.ptr, y.ptr, _stream()))
-            for i in range(len(self.recvs)):
-                _lib.check(L.dnm_mat_mult_remote(self.handle, i, vp(self._recv[i]), y.ptr, _stream()))
+            for i, buf in enumerate(self.recv_buffers(x.array)):
+                _lib.check(L.dnm_mat_mult_remote(self.handle, i, vp(buf), y.ptr, _stream()))
 
     def exchange_only(self, x, y=None):
         """Post and complete the rank exchange of ONE multiply without running any kernel: the same messages over
         the same transport, for measuring what the links sustain (bench.py's ``xgmi_link_GBs_measured``).
         Collective: every rank calls it.  Under the native schedule (``y``: any result vector; it is left alone) the
-        library posts the very groups of its multiply (dnm_comm_set_phase)."""
-        if self.nranks == 1:
+        library posts the very groups of its multiply (dnm_comm_set_phase); without ``y`` the host posts them."""
+        s = self._resolve(x.array.is_cuda)
+        if s == 'local':
             return
         import torch
-        if y is not None and self._native_in_use(x):
+        if s == 'native' and y is not None:
             self._native_phase(x, y, _lib.PHASE_EXCHANGE)
             torch.cuda.synchronize()
             return
-        if self._tr is not None or self._native_tr:
-            _, _, pieces, own, cnt = self._transposed_parts()
+        if self._scheme == 'transpose':
+            _, _, pieces, own, cnt = self._tr or self._native_tr
             xb, wb = self._transpose_buffers(x.array)
             for r in post_transpose(x.array, xb, pieces):        # the state goes out ...
                 r.wait()
             for r in post_transpose(wb, xb, pieces):             # ... and a result of the same size comes back
                 r.wait()
-            if self._native_tr:
+            if s == 'native':
                 self._tr_bufs = None                             # (the library has its own pair)
-        elif not self.partners and self._is_windowed():
+        elif self._scheme == 'window':
             self._setup_windows()
             self._window_buf = exchange_window(x.array if x.internal else x.local_natural(), self._owned, self._windows,
                                                self.rank, self._window_buf, self._needs)
         else:
-            self.prepare_exchange(x.array)
-            bufs = [self._recv[i] for i in range(len(self.recvs))]
-            for r in post_exchange(x.array, self.sends, self.recvs, bufs):
+            for r in post_exchange(x.array, self.sends, self.recvs, self.recv_buffers(x.array)):
                 r.wait()
         if x.array.is_cuda:
             torch.cuda.synchronize()
@@ -1326,26 +1357,19 @@ class ShellMat:
         """Allocate the receive buffers / column window of the partitioned multiply now (they are
         otherwise created by the first ``mult``), so that a solver sizing its Krylov basis to the
         free device memory sees what is really left.  ``like``: a local vector (dtype / device)."""
-        if self.nranks == 1:
-            return
-        import torch
-        if self._native_tr or self._native is not None:
-            if self._native is None:
-                self._native = native_comm()
-            _lib.check(_lib.lib().dnm_comm_prepare(self._native, self.handle, _stream()))
-            return
-        if self._tr is not None:
+        s = self._resolve(like.is_cuda)
+        if s == 'native':
+            _lib.check(_lib.lib().dnm_comm_prepare(self._live_comm(), self.handle, _stream()))
+        elif s == 'transpose':
             self._transpose_buffers(like)
-            return
-        if not self.partners and self._is_windowed():
+        elif s == 'window':
+            import torch
             self._setup_windows()
             lo, hi = self._windows[self.rank]
             if self._window_buf is None or self._window_buf.numel() != hi - lo + 1:
                 self._window_buf = torch.zeros(hi - lo + 1, dtype=like.dtype, device=like.device)
-            return
-        for i, (p, off, cnt) in enumerate(self.recvs):
-            if i not in self._recv:
-                self._recv[i] = torch.empty(cnt, dtype=like.dtype, device=like.device)
+        elif s == 'partner':
+            self.recv_buffers(like)
 
     def uses_cached_diagonal(self):
         """True for the kernels that read a cached diagonal: the SpinConserve kernel (also
@@ -1354,18 +1378,6 @@ class ShellMat:
         if 'SpinConserve kernel' in d or 'SpinConserve row kernel' in d or 'diagonal cached' in d:
             return True
         return 'row-gather kernel' in d
-
-    def _window_splits(self):
-        if self._splits is None:
-            v = C.c_int()
-            _lib.check(_lib.lib().dnm_mat_window_split(self.handle, C.byref(v)))
-            self._splits = bool(v.value)
-        return self._splits
-
-    def _is_windowed(self):
-        """Partitions other than Full/Parity on 2^p ranks: rows split in index order (PetscSplitOwnership), the
-        columns a rank reads come through a window gathered from its neighbours."""
-        return 'tiled=1' not in self.describe()
 
     def column_window(self):
         lo, hi = C.c_int64(), C.c_int64()
@@ -1394,10 +1406,9 @@ class ShellMat:
 
     def _setup_windows(self):
         """Every rank's column window and, inside it, the ranges it really reads (DNM_WINDOW_RANGES=0: the whole
-        window travels)."""
+        window travels); whether the multiply splits into a local and a remote part."""
         if self._windows is not None:
             return
-        import os
         import torch.distributed as dist
         mine = self.column_window()
         needs = self.column_needs(mine) if knob('DNM_WINDOW_RANGES', '1') != '0' else None
@@ -1411,46 +1422,37 @@ class ShellMat:
                 self._owned = [(a // 2, b // 2) for a, b in self._owned]
         else:
             self._owned = [split_ownership(self.N, self.nranks, q) for q in range(self.nranks)]
+        v = C.c_int()
+        _lib.check(_lib.lib().dnm_mat_window_split(self.handle, C.byref(v)))
+        self._splits = bool(v.value)
 
     def _mult_window(self, x, y):
-        """Partitioned SpinConserve: gather the column window, then one kernel."""
+        """Partitioned SpinConserve: gather the column window, then one kernel -- or, where the multiply splits, the
+        part that reads only the rank's own block under the exchange and the rest after it (bpetsc_template_2.c:866-873):
+        two tiled passes in the internal SpinConserve layout (bonds inside a block of equal top bits, the others), or
+        ranges of rows (reference order, Explicit, projections, odd rank counts: stretches of equal top bits, the others)."""
         self._setup_windows()
+        L = _lib.lib()
         # the window is in index order: a swizzled block is straightened first (projection pairs); vectors in the
         # internal SpinConserve layout travel as they lie (the window is a range of the layout)
         xl = x.array if x.internal else x.local_natural()
-        w0 = self._windows[self.rank][0]
-        if self._window_splits():
-            # two tiled passes in the internal SpinConserve layout: the part that reads only what the rank owns (bonds
-            # inside a block of equal top bits, the diagonal) runs while the window is on the links, the rest adds to
-            # it once the window is complete (the reference overlaps assembly and compute block by block,
-            # bpetsc_template_2.c:866-873)
-            L = _lib.lib()
-            self._window_buf, reqs = post_window_exchange(xl, self._owned, self._windows, self.rank, self._window_buf,
-                                                          self._needs)
+        split = self._splits
+        local, remote = ([], []) if split else self._window_row_ranges()
+        self._window_buf, reqs = post_window_exchange(xl, self._owned, self._windows, self.rank, self._window_buf,
+                                                      self._needs)
+        wp, w0, wn = C.c_void_p(self._window_buf.data_ptr()), self._windows[self.rank][0], self._window_buf.numel()
+        if split:
             _lib.check(L.dnm_mat_mult_window_local(self.handle, x.ptr, y.ptr, _stream()))
-            for r in reqs:
-                r.wait()
-            _lib.check(L.dnm_mat_mult_window_remote(self.handle, C.c_void_p(self._window_buf.data_ptr()), w0,
-                                                    self._window_buf.numel(), y.ptr, _stream()))
-            return
-        local, remote = self._window_row_ranges()
-        if local:
-            # reference order, Explicit, projections, odd rank counts: the rows that read only the rank's own block of x
-            # (whole stretches of equal top bits) are multiplied while the window is on the links, the others after
-            L = _lib.lib()
-            self._window_buf, reqs = post_window_exchange(xl, self._owned, self._windows, self.rank, self._window_buf,
-                                                          self._needs)
-            wp, wn = C.c_void_p(self._window_buf.data_ptr()), self._window_buf.numel()
-            for r0, r1 in local:
-                _lib.check(L.dnm_mat_mult_window_rows(self.handle, wp, w0, wn, y.ptr, r0, r1, _stream()))
-            for r in reqs:
-                r.wait()
-            for r0, r1 in remote:
-                _lib.check(L.dnm_mat_mult_window_rows(self.handle, wp, w0, wn, y.ptr, r0, r1, _stream()))
-            return
-        self._window_buf = exchange_window(xl, self._owned, self._windows, self.rank, self._window_buf, self._needs)
-        _lib.check(_lib.lib().dnm_mat_mult_window(self.handle, C.c_void_p(self._window_buf.data_ptr()), w0,
-                                                  self._window_buf.numel(), y.ptr, _stream()))
+        for r0, r1 in local:
+            _lib.check(L.dnm_mat_mult_window_rows(self.handle, wp, w0, wn, y.ptr, r0, r1, _stream()))
+        for r in reqs:
+            r.wait()
+        if split:
+            _lib.check(L.dnm_mat_mult_window_remote(self.handle, wp, w0, wn, y.ptr, _stream()))
+        for r0, r1 in remote:
+            _lib.check(L.dnm_mat_mult_window_rows(self.handle, wp, w0, wn, y.ptr, r0, r1, _stream()))
+        if not split and not local:
+            _lib.check(L.dnm_mat_mult_window(self.handle, wp, w0, wn, y.ptr, _stream()))
 
     WINDOW_ROW_RANGES = 8         # row ranges multiplied under the window exchange, at most
     WINDOW_ROWS_MIN_SHARE = 0.05  # ... if they are at least this share of the rank's rows
@@ -1490,14 +1492,12 @@ class ShellMat:
 
     def destroy(self):
         if self._h is not None:
-            if self._native is not None:
-                # (a communicator released before its operators -- release_native_comm -- has nothing left to forget)
-                if _NATIVE_COMM is not None and self._native.value == _NATIVE_COMM.value:
-                    _lib.check(_lib.lib().dnm_comm_forget(self._native, self._h))
-                self._native = None
+            # (a communicator released before its operators -- release_native_comm -- has nothing left to forget)
+            if self._comm is not None and self._comm[1] == _NATIVE_GEN:
+                _lib.check(_lib.lib().dnm_comm_forget(self._comm[0], self._h))
             _lib.check(_lib.lib().dnm_mat_destroy(self._h))
             self._h = None
-            self._recv = {}
+            self._recv = None
             if self._tr is not None:
                 for h in self._tr[:2]:
                     _lib.check(_lib.lib().dnm_mat_destroy(h))

@@ -29,12 +29,9 @@ def _hooks(mat, keep):
     if d is None:
         return None
     import torch
-    from .backend import Vec, RawVec, native_comm, native_transport
-    if native_transport() and mat._tr is None:
-        # the library's own communicator: multiply and reductions of every solver step stay native (dnm_comm_hooks)
-        mat._native = native_comm()
-        h = _lib.Hooks()
-        _lib.check(_lib.lib().dnm_comm_hooks(mat._native, mat.handle, _stream(), C.byref(h)))
+    from .backend import Vec, RawVec
+    h = mat.native_hooks()          # the library's own communicator: every solver step stays native
+    if h is not None:
         keep.append(h)
         return h
 

@@ -8,7 +8,7 @@ replaces the all-gather of bcuda_template_2.cu:161-171 and the scatters of bpets
   C  post_exchange / post_transpose with the message lists of real plans (rank 0 of 2 partner blocks, rank 1 of 4
      transposed exchange), every peer rewritten to this rank,
   D  evolve and eigsolve with the solver hooks reducing through RCCL, and exchange_only on a world-size-1 operator,
-  F  the same through the native call (dnm_mat_mult_partitioned on the library's own communicator, ShellMat._native),
+  F  the same through the native call (dnm_mat_mult_partitioned on the library's own communicator, ShellMat.bind_native),
   E  the partitioned multiply itself (ShellMat.mult, partner blocks): rank 0 of 2 and rank 5 of 8 of a Full-space
      operator, the state chosen with all rank blocks equal so that what a partner would send is a slice of this rank's
      own block -- the production code posts the exchange on RCCL's stream, runs the rank-local passes under it, waits
@@ -177,7 +177,8 @@ def main():
         xv.set_local_from_numpy(x0)
         px = (C.c_void_p * P)(*[xv.array.data_ptr()] * P)           # all rank blocks equal: every peer's block is this one
         _lib.check(_lib.lib().dnm_comm_loopback(comm, me, P, px, None))
-        mat._native = comm
+        mat.bind_native(comm)
+        assert mat.schedule == "native"
         yv.set(3.0)
         mat.mult(xv, yv)
         torch.cuda.synchronize()

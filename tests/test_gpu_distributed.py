@@ -87,7 +87,7 @@ def _worker(rank, world, port, case, out_dir):
         # and the last rank own long stretches of equal top bits
         # (a host-schedule attribute; the native schedule makes the same split inside the library)
         local, remote = H.get_mat()._row_ranges or ([], [])
-        if rank in (0, world - 1) and H.get_mat()._native is None:
+        if rank in (0, world - 1) and H.get_mat().schedule != "native":
             assert local and remote and sum(b - a for a, b in local) > 0.05 * H.get_mat().m_local, (local, remote)
         z = H.evolve(x, t=0.3, algo='chebyshev')
         assert abs(z.norm() - 1) < 1e-9 and abs(z.dot(H.dot(z)).imag) < 1e-9
@@ -249,7 +249,9 @@ def _worker(rank, world, port, case, out_dir):
             assert "table records: " in H.get_mat().describe() or want_scheme == "transpose", H.get_mat().describe()
         if want_scheme == "transpose" and case in ("full", "parity"):
             # ... and runs sub-piece by sub-piece (forward parts, ranges of the layout-B pass, returns)
-            assert H.get_mat()._tr_pipe or H.get_mat()._native_tr, "the transposed exchange should pipeline at this size"
+            # (the library's split: the native schedule of a transposed exchange)
+            assert H.get_mat().transpose_pipelined or H.get_mat().schedule == "native", \
+                "the transposed exchange should pipeline at this size"
     y = H.dot(x)
     yg = y.to_numpy(to_all=True)
     ref = orc.matvec(orc_msc(H), orc_sub(sub), orc_sub(sub), xg, nthreads=2)
@@ -366,7 +368,7 @@ def _worker(rank, world, port, case, out_dir):
         y1 = _b.Vec(dim, swz=m1.swz_left, sub_c=d1)
         m1.mult(x1, y1)
         if os.environ.get("DNM_NATIVE_COMM") == "1":
-            assert m1._native is not None
+            assert m1.schedule == "native"
         parts = _cm.gather_varied(y1.array, [s_[1] for s_ in shares], dst=0)
         if rank == 0:
             yfull = torch.cat(parts)
@@ -457,12 +459,22 @@ def _native_ran(H, case):
     mats = [m for k, m in H._mats.items() if m is not None and k not in idle]
     assert mats
     for m in mats:
-        assert m._native is not None, "the native schedule did not run (%s)" % case
-        assert m._tr is None, "the host's transposed schedule was built beside the native one (%s)" % case
-    # the operators go first, then the communicator (the stand-in transport removes its mailboxes with the last rank)
-    from dynamite_amd import backend
+        # (an operator with the host's transposed split resolves to that schedule, never to the native one)
+        assert m.schedule != "transpose", "the host's transposed schedule was built beside the native one (%s)" % case
+        assert m.schedule == "native", "the native schedule did not run (%s)" % case
+    # the operators go first, then the communicator (the stand-in transport removes its mailboxes with the last rank) --
+    # but for one, kept past the release: it refuses the native schedule without calling the library, and is destroyed
+    import torch
+    from dynamite_amd import backend, config
+    kept = H._mats.pop(next(k for k, m in H._mats.items() if m is mats[0]))
     H.destroy_mat()
     backend.release_native_comm()
+    x, y = (backend.RawVec(torch.zeros(n, dtype=torch.complex128, device=config.device), swz)
+            for n, swz in ((kept.n_local, kept.swz_right), (kept.m_local, kept.swz_left)))
+    x.perm, y.perm = kept.perm_right, kept.perm_left
+    with pytest.raises(RuntimeError, match="release_native_comm"):
+        kept.mult(x, y)
+    kept.destroy()
 
 
 FAKE_RCCL = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")

@@ -159,7 +159,7 @@ def test_shellmat_reports_the_native_transposed_exchange_like_the_host_one(L, P)
         m2 = backend.ShellMat(h2, sc, sc, P, rank)
         m2.set_transposed(backend.transpose_split(*arrs, L, P, 0), sc, sc, _lib.MAT_HOST_ONLY)
         assert m.exchange_summary() == m2.exchange_summary() and m.exchange_summary()["scheme"] == "transpose"
-        assert m2._tr_pipe and m.launches_per_mult() == m2.launches_per_mult()
+        assert m2.transpose_pipelined and m.launches_per_mult() == m2.launches_per_mult()
         m.destroy()
         m2.destroy()
 

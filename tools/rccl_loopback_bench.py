@@ -104,8 +104,8 @@ def main():
         t_local = timed(lambda: _lib.check(L_.dnm_mat_mult_local(mat.handle, x.ptr, y.ptr, backend._stream())))
 
         def remote_only():
-            for i in range(len(mat.recvs)):
-                _lib.check(L_.dnm_mat_mult_remote(mat.handle, i, backend.C.c_void_p(mat._recv[i].data_ptr()), y.ptr,
+            for i, buf in enumerate(mat.recv_buffers(x.array)):
+                _lib.check(L_.dnm_mat_mult_remote(mat.handle, i, backend.C.c_void_p(buf.data_ptr()), y.ptr,
                                                   backend._stream()))
         t_remote = timed(remote_only)
         print("   multiply with the exchange looped back over RCCL: %.2f ms; exchange alone %.2f ms (%.0f GB/s through RCCL's "
@@ -130,24 +130,32 @@ def main():
             mat2 = backend.ShellMat(h2, c2, c2, P, me)
             split = backend.transpose_split(masks, offs, H.msc['signs'], H.msc['coeffs'], L, P, S, 0)
             assert split is not None
-            mat2.set_transposed(split, c2, c2, 0)
-            lo_h, hi_h, pieces, own, cnt = mat2._tr
-            mat2._tr = (lo_h, hi_h, [(0, off, c_) for _, off, c_ in pieces], own, cnt)
+            pieces_of = backend.transpose_pieces
+
+            def looped(*a):           # every piece of the all-to-all addressed to this process
+                pieces, own, cnt = pieces_of(*a)
+                return [(0, off, c_) for _, off, c_ in pieces], own, cnt
+            backend.transpose_pieces = looped
+            try:
+                mat2.set_transposed(split, c2, c2, 0)
+            finally:
+                backend.transpose_pieces = pieces_of
             x, y = backend.Vec(n_loc, swz=S), backend.Vec(n_loc, swz=S)
             x.set_random(1)
             t_tr = timed(lambda: mat2.mult(x, y))
             t_ex = timed(lambda: mat2.exchange_only(x))
-            moved = 2 * 16 * cnt * len(pieces)
+            moved = mat2.exchange_summary()["bytes_in"]
             print("   transposed exchange looped back (swizzle %d, %s): %.2f ms per multiply; its two all-to-alls alone %.2f ms "
                   "(%.1f GiB, %.0f GB/s through RCCL's copies)"
-                  % (S, "pipelined" if mat2._tr_pipe else "whole pieces", t_tr, t_ex, moved / 2 ** 30, moved / t_ex / 1e6), flush=True)
-            # ... and split and scheduled inside the library (dnm_mat_set_exchange + dnm_mat_mult_partitioned): the host's
-            # buffers go first (the library has its own pair), every peer's block = this rank's x, no peer handles
-            # (the returning pieces carry this rank's own result)
-            for h_ in mat2._tr[:2]:
-                _lib.check(_lib.lib().dnm_mat_destroy(h_))
-            mat2._tr, mat2._tr_bufs = None, None
+                  % (S, "pipelined" if mat2.transpose_pipelined else "whole pieces", t_tr, t_ex, moved / 2 ** 30,
+                     moved / t_ex / 1e6), flush=True)
+            # ... and split and scheduled inside the library (dnm_mat_set_exchange + dnm_mat_mult_partitioned) on an operator
+            # of its own: the host's handles and buffers go first (the library has its own pair), every peer's block = this
+            # rank's x, no peer handles (the returning pieces carry this rank's own result)
+            mat2.destroy()
             torch.cuda.empty_cache()
+            mat2 = backend.ShellMat(backend.create_mat(masks, offs, H.msc['signs'], H.msc['coeffs'], c2, c2, False, 0, me, P),
+                                    c2, c2, P, me)
             assert mat2.set_native_transposed()
             px = (C.c_void_p * P)(*[x.array.data_ptr()] * P)
             _lib.check(_lib.lib().dnm_comm_loopback(comm, me, P, px, None))
