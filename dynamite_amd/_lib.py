@@ -91,7 +91,7 @@ MAT_REAL_PACKED = 16      # real arithmetic for a real-symmetric operator: vecto
 EXCHANGE_AUTO, EXCHANGE_PARTNER, EXCHANGE_TRANSPOSE = 0, 1, 2      # dnm_mat_set_exchange
 PHASE_ALL, PHASE_EXCHANGE, PHASE_COMPUTE = 0, 1, 2                  # dnm_comm_set_phase
 MAT_AMIN_SHIFT = 8        # flags bits 8..15: log2 of the contiguous run of a window tile
-WHICH = {"lowest": 0, "highest": 1, "exterior": 2}
+WHICH = {"lowest": 0, "highest": 1, "exterior": 2, "target": 3}
 CONVERGED_TOL, CONVERGED_ITS, DIVERGED_ITS, DIVERGED_BREAKDOWN, DIVERGED_SYMMETRY_LOST = 1, 2, -1, -2, -3
 
 # name -> (restype, argtypes); every symbol include/dynamite_amd.h declares
@@ -199,6 +199,11 @@ SIGNATURES = {
     "dnm_eigsolve": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                C.c_uint64, C.POINTER(Hooks), C.c_int, f64p, vp,
                                C.POINTER(SolverStats), vp]),
+    "dnm_eigsolve_interior": (C.c_int, [vp, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                        C.c_uint64, C.POINTER(Hooks), C.c_int, f64p, vp,
+                                        C.POINTER(SolverStats), vp]),
+    "dnm_interior_filter_plan": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.POINTER(C.c_int), f64p, f64p]),
 }
 
 

@@ -266,18 +266,28 @@ def _evolve_chebyshev(H, state, t, result, tol):
 
 
 def eigsolve(H, getvecs=False, nev=1, which='lowest', target=None, tol=None, subspace=None,
-             max_its=None, ncv=None, seed=0):
-    """A few extremal eigenpairs (computations.py:128-292)."""
+             max_its=None, ncv=None, seed=0, interior=None):
+    """A few extremal eigenpairs (computations.py:128-292), or -- ``target=E, interior='filter'``, not in the
+    reference, whose only interior method is shift-invert on a stored matrix -- the ``nev`` eigenpairs nearest
+    ``E``, matrix-free, by a Chebyshev filter of the folded spectrum (dnm_eigsolve_interior): ordered by
+    ``|E_i - target|``, converged when ``|H v - E_i v| <= tol * ||H||_inf``.  Without ``interior``, ``target`` is
+    refused as the reference refuses it for shell matrices."""
     H.establish_L()
     if subspace is None:
         subspace = H.subspace
     elif not H.has_subspace(subspace):
         raise ValueError('Requested subspace has not been added to operator.')
-    config._initialize()
-    if target is not None:
+    if interior is not None and interior != 'filter':
+        raise ValueError(f'invalid value "{interior}" for interior (the matrix-free interior method is "filter")')
+    if interior is not None and target is None:
+        raise ValueError("Must specify target when setting interior='filter'")
+    if target is not None and interior is None:
         # computations.py:211-220: refused for shell matrices and on GPUs
         raise RuntimeError('Shift-invert ("target") not supported for shell matrices.')
-    if which == 'target':
+    config._initialize()
+    if target is not None:
+        which = 'target'              # computations.py:208-213: a target decides what "which" means
+    elif which == 'target':
         raise ValueError("Must specify target when setting which='target'")
     if which in ['smallest', 'largest']:
         warnings.warn('values "smallest" and "largest" for eigsolve parameter "which" '
@@ -334,8 +344,9 @@ def eigsolve(H, getvecs=False, nev=1, which='lowest', target=None, tol=None, sub
     import os
     ncv_native = 0 if ncv is None else int(ncv)
     bf = knob('DNM_EIGS_BASISFREE')
-    basis_free = (ncv is None and nev == 1 and mat.N > 64 and
+    basis_free = (ncv is None and nev == 1 and mat.N > 64 and interior is None and
                   (bf[:1] == '1' if bf else _min_over_ranks(mat.n_local) >= (1 << 22)))
+    work_vecs = 4 if interior else 3      # beside the basis: the residual vector and the filter's work vectors
     if ncv is None and not basis_free:
         # SLEPc's default max(2 nev, nev + 15) (+1 for the residual vector), reduced to what fits in HBM
         cached = C.c_size_t()
@@ -347,10 +358,16 @@ def eigsolve(H, getvecs=False, nev=1, which='lowest', target=None, tol=None, sub
             # multiply's own vectors, freed by the caller but still in torch's cache, once made a solve at
             # SpinConserve(33,16) run out of memory with "17 fit")
             free, _ = torch.cuda.mem_get_info()
-            return int((free + cached.value) // vec_bytes) - 3 - (nev_max if getvecs else 0)
+            return int((free + cached.value) // vec_bytes) - work_vecs - (nev_max if getvecs else 0)
         torch.cuda.empty_cache()            # memory torch holds for reuse counts as free
         fit = _min_over_ranks(fitting())
-        if fit < want:
+        if fit < want and interior:
+            if fit < nev + 2:
+                raise RuntimeError('not enough device memory for eigsolve(nev=%d, target=%g): %d vectors of %.1f GiB '
+                                   'fit, the filtered solver needs %d' % (nev, target, max(fit + work_vecs, 0),
+                                                                          vec_bytes / 2 ** 30, nev + 2 + work_vecs))
+            ncv_native = -(fit + work_vecs)
+        elif fit < want:
             if fit < nev + 5:
                 # no room for a restarted basis worth the name (at least nev + 2 vectors beside the Chebyshev filter's
                 # work vectors): the native driver takes the pairs one after the other through the basis-free
@@ -371,11 +388,16 @@ def eigsolve(H, getvecs=False, nev=1, which='lowest', target=None, tol=None, sub
         from .backend import device_zeros
         evec_buf = device_zeros(nev_max * mat.n_local, empty=True)
     stats = _lib.SolverStats()
-    _lib.check(_lib.lib().dnm_eigsolve(
-        mat.handle, mat.n_local, int(nev), _lib.WHICH[which], 0.0 if tol is None else float(tol),
-        ncv_native, 0 if max_its is None else int(max_its), int(seed),
-        C.byref(hooks) if hooks is not None else None, nev_max, _lib.pf64(evals),
-        C.c_void_p(evec_buf.data_ptr()) if evec_buf is not None else None, C.byref(stats), _stream()))
+    tail = (ncv_native, 0 if max_its is None else int(max_its), int(seed),
+            C.byref(hooks) if hooks is not None else None, nev_max, _lib.pf64(evals),
+            C.c_void_p(evec_buf.data_ptr()) if evec_buf is not None else None, C.byref(stats), _stream())
+    if interior:
+        _lib.check(_lib.lib().dnm_eigsolve_interior(
+            mat.handle, mat.n_local, int(nev), float(target), 0.0 if tol is None else float(tol), *tail))
+    else:
+        _lib.check(_lib.lib().dnm_eigsolve(
+            mat.handle, mat.n_local, int(nev), _lib.WHICH[which], 0.0 if tol is None else float(tol), *tail))
+    # (max_rel_residual: relative to |E_i| for the extremal solver, to ||H||_inf for the interior one)
     eigsolve.last_stats = {'reason': stats.reason, 'its': stats.its, 'matvecs': stats.matvecs,
                            'nconv': stats.nconv, 'max_rel_residual': stats.err_est, 'real_arithmetic': packed}
     nconv = stats.nconv

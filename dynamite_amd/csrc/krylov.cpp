@@ -158,6 +158,55 @@ static void jacobi_eig(int n, std::vector<double> &A, std::vector<double> &w, st
   for (int i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
 }
 
+// Eigen-decomposition of a small Hermitian matrix (row-major n x n, destroyed) by cyclic Jacobi rotations
+// J = [[c, s ph], [-s conj(ph), c]], ph = a_pq / |a_pq|: w the eigenvalues (unsorted), Q[c * n + k] component k of
+// eigenvector c -- the layout jacobi_eig uses.  The Rayleigh-Ritz step of the interior solver in H, whose projected
+// matrix is complex for a complex operator.
+static void hjacobi_eig(int n, std::vector<zc> &A, std::vector<double> &w, std::vector<zc> &Q) {
+  Q.assign((size_t)n * n, zc(0));
+  for (int i = 0; i < n; ++i) Q[(size_t)i * n + i] = 1.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0, dg = 0.0;
+    for (int p = 0; p < n; ++p) {
+      dg += std::norm(A[(size_t)p * n + p]);
+      for (int q = p + 1; q < n; ++q) off += std::norm(A[(size_t)p * n + q]);
+    }
+    if (off <= 1e-34 * (dg + off)) break;
+    for (int p = 0; p < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const zc apq = A[(size_t)p * n + q];
+        const double g = std::abs(apq);
+        const double app = A[(size_t)p * n + p].real(), aqq = A[(size_t)q * n + q].real();
+        if (g <= 1e-300 || g <= 1e-20 * (std::fabs(app) + std::fabs(aqq))) continue;
+        const zc ph = apq / g;
+        const double tau = (aqq - app) / (2.0 * g);
+        const double t = (tau >= 0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
+        const zc sp = s * ph, spc = s * std::conj(ph);
+        for (int k = 0; k < n; ++k) {           // columns p, q: A <- A J
+          const zc akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
+          A[(size_t)k * n + p] = c * akp - spc * akq;
+          A[(size_t)k * n + q] = sp * akp + c * akq;
+        }
+        for (int k = 0; k < n; ++k) {           // rows p, q: A <- J^H A
+          const zc apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
+          A[(size_t)p * n + k] = c * apk - sp * aqk;
+          A[(size_t)q * n + k] = spc * apk + c * aqk;
+        }
+        A[(size_t)p * n + q] = A[(size_t)q * n + p] = 0;
+        A[(size_t)p * n + p] = A[(size_t)p * n + p].real();
+        A[(size_t)q * n + q] = A[(size_t)q * n + q].real();
+        for (int k = 0; k < n; ++k) {           // eigenvectors: Q <- Q J (stored transposed)
+          const zc vkp = Q[(size_t)p * n + k], vkq = Q[(size_t)q * n + k];
+          Q[(size_t)p * n + k] = c * vkp - spc * vkq;
+          Q[(size_t)q * n + k] = sp * vkp + c * vkq;
+        }
+      }
+  }
+  w.resize(n);
+  for (int i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i].real();
+}
+
 // ---------------------------------------------------------------------------
 // distributed plumbing
 // ---------------------------------------------------------------------------
@@ -197,6 +246,21 @@ struct ChebFilter {
   }
 };
 
+// Folded-spectrum filter for interior eigenpairs: with G = (A - sigma)^2 the eigenvalues within `a` of sigma are the
+// lowest of G, in [0, a^2), the rest lies in [a^2, h^2], h = max(sigma - emin, emax - sigma).  The filter is
+//   p(A) = T_d((G - c) / e) / T_d(-c / e),   c = (h^2 + a^2) / 2,  e = (h^2 - a^2) / 2:
+// |p| <= 1 / T_d(c / e) on the unwanted part, p(sigma) = 1, monotone in |lambda - sigma| inside the window.
+// G - c = (A - (sigma + sqrt c)) (A - (sigma - sqrt c)), so a term of the recurrence is two fused multiplies
+// (Ops::apply_fold); the numbers come from dnm_interior_filter_plan.
+struct FoldFilter {
+  int d = 0;
+  double sigma = 0, c = 0, e = 0;
+  void *ta = nullptr, *tb = nullptr, *tc = nullptr;     // three work vectors
+  bool on = false;
+  double theta0() const { return std::acosh(c / e); }
+  double bound() const { return 1.0 / std::cosh(d * theta0()); }      // |p| on the unwanted part
+};
+
 struct Ops {
   dnm_mat *A;
   const dnm_hooks *hooks;
@@ -204,6 +268,7 @@ struct Ops {
   int64_t n;
   int matvecs = 0;
   ChebFilter *flt = nullptr;
+  FoldFilter *fold = nullptr;
   // real-packed operator (DNM_MAT_REAL_PACKED): the vectors are real, two amplitudes to a complex128 element; the
   // real part of the complex inner product of two such vectors IS their real inner product, its imaginary part
   // means nothing and is dropped wherever an inner product comes back
@@ -246,7 +311,63 @@ struct Ops {
     return vk_scale(y, n, std::exp(logscale), 0, st);
   }
 
+  // y = A x - b z + c2 z2 (z2 may be null): one fused multiply, or the multiply through the hook and a sweep per term
+  int fold_step(const void *x, void *y, const void *z, double b, const void *z2, double c2) {
+    ++matvecs;
+    if (hooks && hooks->mult) {
+      DNM_CHECK(hooks->mult(hooks->ctx, x, y) == 0, "mult hook failed");
+      DNM_TRY(vk_axpby(y, z, n, -b, 0.0, 1.0, 0.0, st));
+      if (z2) DNM_TRY(vk_axpby(y, z2, n, c2, 0.0, 1.0, 0.0, st));
+      return 0;
+    }
+    return dnm_mat_mult_sub2(A, x, y, z, b, z2, c2, 0.0, (void *)st);
+  }
+  // y = p(A) x for the folded filter; y must differ from x and from the three work vectors.  Unnormalised terms
+  // u_j = e^j T_j / 2^(j-1) as in apply_filter (u_1 = (G - c) u_0, u_2 = (G - c) u_1 - (e^2 / 2) u_0,
+  // u_{j+1} = (G - c) u_j - (e / 2)^2 u_{j-1}), each (G - c) u = (A - b2)(A - b1) u through the work vector tc; the
+  // growth by e / 2 per term is taken out of the two live vectors whenever it passes 1e100 (the degree runs to
+  // thousands).  scale_out as in apply_filter.
+  int apply_fold(const void *x, void *y, double *scale_out = nullptr) {
+    const FoldFilter &F = *fold;
+    const double rc = std::sqrt(F.c), b1 = F.sigma - rc, b2 = F.sigma + rc;
+    void *buf[3] = {F.ta, F.tb, y};
+    const int first = (3 - (F.d % 3)) % 3;
+    const void *um = nullptr, *uc = x;
+    const double lstep = std::log(0.5 * F.e);
+    // (a rescaling touches the two live vectors: after the first term one of them is still the caller's x)
+    DNM_CHECK(std::fabs(lstep) < 100.0, "interior filter: spectral interval out of range (e = %g)", F.e);
+    double lgrow = 0.0, ltaken = 0.0;         // log of the growth since the last rescaling / of what was taken out
+    for (int j = 1; j <= F.d; ++j) {
+      void *out = buf[(first + j - 1) % 3];
+      const double b = j == 1 ? 0.0 : (j == 2 ? 0.5 * F.e * F.e : 0.25 * F.e * F.e);
+      DNM_TRY(fold_step(uc, F.tc, uc, b1, nullptr, 0.0));
+      DNM_TRY(fold_step(F.tc, out, F.tc, b2, j == 1 ? nullptr : um, -b));
+      um = uc;
+      uc = out;
+      lgrow += lstep;
+      if (std::fabs(lgrow) > 230.0 && j < F.d) {
+        // (j >= 3 here, since |lstep| < 100: um and uc are work vectors, never x)
+        const double f = std::exp(-lgrow);
+        DNM_TRY(vk_scale(buf[(first + j - 1) % 3], n, f, 0, st));
+        DNM_TRY(vk_scale(buf[(first + j - 2) % 3], n, f, 0, st));
+        ltaken += lgrow;
+        lgrow = 0.0;
+      }
+    }
+    // T_d(-c / e) = (-1)^d cosh(d acosh(c / e))
+    const double dth = F.d * F.theta0();
+    const double logT = dth - std::log(2.0) + std::log1p(std::exp(-2.0 * dth));
+    const double logscale = ltaken - (F.d * std::log(F.e) - (F.d - 1) * std::log(2.0)) - logT;
+    const double sc = ((F.d & 1) ? -1.0 : 1.0) * std::exp(logscale);
+    if (scale_out) {
+      *scale_out = sc;
+      return 0;
+    }
+    return vk_scale(y, n, sc, 0, st);
+  }
+
   int mult(const void *x, void *y) {
+    if (fold && fold->on) return apply_fold(x, y);
     if (flt && flt->on) return apply_filter(x, y);
     ++matvecs;
     if (hooks && hooks->mult) {
@@ -1708,6 +1829,338 @@ int dnm_eigsolve(dnm_mat *A, int64_t n_local, int nev, int which, double tol, in
   stats->matvecs = ops.matvecs;
   stats->nconv = nout;
   stats->reason = (nconv >= nev) ? DNM_CONVERGED_TOL : DNM_DIVERGED_ITS;
+  return 0;
+}
+
+int dnm_interior_filter_plan(double emin, double emax, double target, double a, double damping, int *degree,
+                             double *c, double *e) {
+  DNM_CHECK(degree && c && e, "null argument");
+  DNM_CHECK(emax > emin && a > 0 && damping > 1, "bad argument (emax > emin, a > 0, damping > 1)");
+  const double h = std::max(target - emin, emax - target);
+  DNM_CHECK(h > a, "the window [target - a, target + a] covers the whole interval");
+  *c = 0.5 * (h * h + a * a);
+  *e = 0.5 * (h * h - a * a);
+  const double d = std::ceil(std::acosh(damping) / std::acosh(*c / *e));
+  DNM_CHECK(d < 1e9, "filter degree out of range (window too narrow for the interval)");
+  *degree = std::max(1, (int)d);
+  return 0;
+}
+
+int dnm_eigsolve_interior(dnm_mat *A, int64_t n_local, int nev, double target, double tol, int ncv, int max_its,
+                          uint64_t seed, const dnm_hooks *hooks, int nev_max, double *evals, void *evecs,
+                          dnm_solver_stats *stats, void *stream) {
+  DNM_CHECK(A && evals && stats && nev >= 1 && nev_max >= nev, "bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  Ops ops{A, hooks, st, n_local};
+  ops.real = A->real_packed;
+  stats->reason = 0; stats->its = 0; stats->matvecs = 0; stats->nconv = 0; stats->err_est = 0;
+  // (a real-packed handle counts complex128 elements, two amplitudes each)
+  const int64_t Nglob = A->real_packed ? 2 * A->N : A->N;
+  if (tol <= 0) tol = 1e-8;
+  DNM_CHECK(Nglob >= (int64_t)nev + 3, "operator too small for %d interior pairs (dimension %lld)", nev, (long long)Nglob);
+  // basis: ncv as in dnm_eigsolve (ncv < 0: at most -ncv vectors in all); beside the m + 1 Lanczos vectors the
+  // filter keeps three work vectors
+  int cap = 0;
+  if (ncv < 0) { cap = -ncv; ncv = 0; }
+  int m = ncv > 0 ? ncv : std::max(2 * nev, nev + 15);
+  if (cap > 0 && m + 4 > cap) m = cap - 4;
+  if ((int64_t)m > Nglob - 1) m = (int)(Nglob - 1);
+  {
+    double neg = -(double)m;          // the same basis size on every rank
+    DNM_TRY(ops.maxr(&neg, 1));
+    m = (int)(-neg);
+  }
+  DNM_CHECK(m >= nev + 2, "not enough memory for a restarted basis of %d interior pairs (%d vectors fit beside the "
+            "filter's three)", nev, std::max(m, 0));
+  DNM_CHECK((size_t)(m + 1) * 16 <= 160 * 1024, "ncv too large for the basis-rotation kernel");
+  if (max_its <= 0) max_its = 100;
+  if (nev_max > m - 1) nev_max = m - 1;
+
+  void *V = nullptr;
+  DNM_TRY(basis_workspace((size_t)(m + 4) * (size_t)n_local * 16, &V));
+  FoldFilter F;
+  F.sigma = target;
+  F.ta = vecptr(V, n_local, m + 1);
+  F.tb = vecptr(V, n_local, m + 2);
+  F.tc = vecptr(V, n_local, m + 3);
+  ops.fold = &F;
+  const bool debug = knob("DNM_KRYLOV_DEBUG") != nullptr;
+
+  double nrmH = 0;
+  DNM_TRY(dnm_mat_norm_inf(A, &nrmH, (void *)st));
+  DNM_TRY(ops.maxr(&nrmH, 1));
+  DNM_CHECK(nrmH > 0, "zero operator");
+
+  // ---- the ends of the spectrum and the density of states near the target: one plain Lanczos run -----------------
+  // Its extreme Ritz values lie inside the spectrum, each within its residual of an eigenvalue; the squared first
+  // components of the Ritz vectors are the weights of a Gauss quadrature of the spectral measure of the (random)
+  // start vector, i.e. of the density of states: the window half-width `a` is where that estimate counts
+  // nev + margin levels around the target.
+  const int64_t offset = hooks ? A->row0 : 0;
+  double emin = 0, emax = 0, a = 0;
+  {
+    const int k0 = (int)std::min<int64_t>(Nglob - 1, std::max(60, 4 * nev));
+    std::vector<double> al, be;
+    auto slot = [&](int k) { return (void *)vecptr(V, n_local, k % 3); };
+    DNM_TRY(random_start(A, slot(0), n_local, seed, offset, st));
+    double nrm0 = 0;
+    DNM_TRY(ops.norm(slot(0), &nrm0));
+    DNM_CHECK(nrm0 > 0, "zero start vector");
+    DNM_TRY(vk_scale(slot(0), n_local, 1.0 / nrm0, 0, st));
+    for (int j = 0; j < k0; ++j) {
+      void *q = slot(j), *pq = slot(j + 1), *qm = slot(j + 2);
+      zc dd(0);
+      DNM_TRY(ops.mult_dot(q, pq, &dd, j > 0 ? qm : nullptr, j > 0 ? be[j - 1] : 0.0, nullptr));
+      al.push_back(dd.real());
+      double n2 = 0;
+      DNM_TRY(vec_lanczos_update_host(pq, q, nullptr, n_local, dd.real(), dd.imag(), 0.0, &n2, st, 1.0));
+      DNM_TRY(ops.sum(&n2, 1));
+      const double bn = std::sqrt(n2 > 0 ? n2 : 0.0);
+      be.push_back(bn);
+      if (bn <= 1e-12 * nrmH) break;
+      DNM_TRY(vk_scale(pq, n_local, 1.0 / bn, 0, st));
+    }
+    const int kk = (int)al.size();
+    std::vector<double> Tm((size_t)kk * kk, 0.0), wv, Sv;
+    for (int i = 0; i < kk; ++i) {
+      Tm[(size_t)i * kk + i] = al[i];
+      if (i + 1 < kk) Tm[(size_t)(i + 1) * kk + i] = Tm[(size_t)i * kk + i + 1] = be[i];
+    }
+    jacobi_eig(kk, Tm, wv, Sv);
+    std::vector<int> ord(kk);
+    for (int i = 0; i < kk; ++i) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int x, int y) { return wv[x] < wv[y]; });
+    const int ilo = ord[0], ihi = ord[kk - 1];
+    const double width = std::max(wv[ihi] - wv[ilo], 1e-3 * nrmH);
+    // outward by the residual of the extreme Ritz pair and one per cent of the width: a bound that is too tight makes
+    // p blow up (checked on a probe vector below), one that is too wide costs degree in proportion
+    emin = std::max(-nrmH, wv[ilo] - be[kk - 1] * std::fabs(Sv[(size_t)ilo * kk + kk - 1]) - 0.01 * width);
+    emax = std::min(nrmH, wv[ihi] + be[kk - 1] * std::fabs(Sv[(size_t)ihi * kk + kk - 1]) + 0.01 * width);
+    // cumulative weight at the Ritz values (midpoint rule), linear in between
+    std::vector<double> ws(kk), cum(kk);
+    double acc = 0.0;
+    for (int i = 0; i < kk; ++i) {
+      const double wt = Sv[(size_t)ord[i] * kk] * Sv[(size_t)ord[i] * kk];
+      ws[i] = wv[ord[i]];
+      cum[i] = acc + 0.5 * wt;
+      acc += wt;
+    }
+    auto cdf = [&](double E) {
+      if (E <= ws[0]) return 0.0;
+      if (E >= ws[kk - 1]) return 1.0;
+      const int i = (int)(std::upper_bound(ws.begin(), ws.end(), E) - ws.begin());     // ws[i-1] <= E < ws[i]
+      const double t = (E - ws[i - 1]) / std::max(ws[i] - ws[i - 1], 1e-300);
+      return cum[i - 1] + t * (cum[i] - cum[i - 1]);
+    };
+    const double nwant = nev + std::max(4, nev / 2);
+    const double hfull = std::max(target - emin, emax - target);
+    double lo = 0.0, hi = hfull;
+    for (int it = 0; it < 60; ++it) {
+      const double mid = 0.5 * (lo + hi);
+      if ((double)Nglob * (cdf(target + mid) - cdf(target - mid)) < nwant) lo = mid; else hi = mid;
+    }
+    a = std::min(hi, 0.5 * hfull);
+    // DNM_EIGS_INTERIOR_WINDOW=f (experiments): the estimate times f -- f < 1 starts from a window with too few
+    // levels, which the widening below has to repair (tests)
+    if (const char *we = knob("DNM_EIGS_INTERIOR_WINDOW")) a = std::min(a * std::max(atof(we), 1e-3), 0.5 * hfull);
+    a = std::max(a, 1e-6 * hfull);
+    if (debug)
+      fprintf(stderr, "dnm_eigsolve_interior: %d probe steps, spectrum in [%.6g, %.6g] (|H|_inf %.6g), half-width %.4g "
+              "for about %.0f levels\n", kk, emin, emax, nrmH, a, nwant);
+  }
+
+  const double damping = 100.0;        // |p| <= 1 / damping outside the window: the nev-th wanted value, at about
+                                       // two thirds of the half-width, stands cosh(0.745 acosh(100)) = 26 above it
+  auto plan = [&]() -> int { return dnm_interior_filter_plan(emin, emax, target, a, damping, &F.d, &F.c, &F.e); };
+  DNM_TRY(plan());
+
+  // ---- start vector: p(A) of a random vector, which also shows whether the bounds hold (|p| <= 1 on the spectrum) ---
+  F.on = true;
+  for (int attempt = 0;; ++attempt) {
+    void *x = vecptr(V, n_local, 1), *px = vecptr(V, n_local, 0);
+    DNM_TRY(random_start(A, x, n_local, seed + 1, offset, st));
+    double nx = 0, npx = 0;
+    DNM_TRY(ops.norm(x, &nx));
+    DNM_CHECK(nx > 0, "zero start vector");
+    DNM_TRY(vk_scale(x, n_local, 1.0 / nx, 0, st));
+    DNM_TRY(ops.apply_fold(x, px));
+    DNM_TRY(ops.norm(px, &npx));
+    if (debug) fprintf(stderr, "dnm_eigsolve_interior: degree %d, |p(A) x| = %.3g on a unit probe vector\n", F.d, npx);
+    if (std::isfinite(npx) && npx <= 1.5 && npx > 0) {
+      DNM_TRY(vk_scale(px, n_local, 1.0 / npx, 0, st));
+      break;
+    }
+    DNM_CHECK(attempt < 6 && (emin > -nrmH || emax < nrmH), "the interior filter is unbounded on the operator's "
+              "spectrum (bounds [%.6g, %.6g])", emin, emax);
+    const double wdt = emax - emin;
+    emin = std::max(-nrmH, emin - 0.05 * wdt);
+    emax = std::min(nrmH, emax + 0.05 * wdt);
+    DNM_TRY(plan());
+  }
+
+  // ---- thick-restart Lanczos on p(A), every vector against the whole basis -----------------------------------------
+  std::vector<double> theta, spike, alpha(m, 0.0), betav(m, 0.0), T, w, Sm;
+  std::vector<int> order(m);
+  std::vector<zc> h;
+  int l = 0, its = 0, nok = 0, widenings = 0, extra_matvecs = 0;
+  double tol_p = tol, worst = 0.0;
+  std::vector<double> rth;              // Ritz values in H of the last Rayleigh-Ritz step, nearest the target first
+  std::vector<zc> rQ;                   // ... and their vectors in the basis V[:, 0:nrr)
+  int nrr = 0;
+  while (true) {
+    ++its;
+    for (int j = l; j < m; ++j) {
+      void *p = vecptr(V, n_local, j + 1);
+      DNM_TRY(ops.mult(vecptr(V, n_local, j), p));
+      double bn = 0;
+      DNM_TRY(ops.orthogonalize(p, V, j + 1, h, &bn, 2));
+      alpha[j] = h[j].real();
+      betav[j] = bn;
+      if (!(bn > 1e-14)) {           // (p(A) has norm 1) invariant subspace: a fresh direction orthogonal to the basis
+        betav[j] = 0.0;
+        DNM_TRY(random_start(A, p, n_local, seed + 7919u * (uint64_t)(its * m + j + 1), offset, st));
+        double rn = 0;
+        DNM_TRY(ops.orthogonalize(p, V, j + 1, h, &rn, 2));
+        DNM_CHECK(rn > 0, "Lanczos breakdown: could not extend the basis");
+        DNM_TRY(vk_scale(p, n_local, 1.0 / rn, 0, st));
+      } else {
+        DNM_TRY(vk_scale(p, n_local, 1.0 / bn, 0, st));
+      }
+    }
+    T.assign((size_t)m * m, 0.0);
+    for (int i = 0; i < l; ++i) {
+      T[(size_t)i * m + i] = theta[i];
+      T[(size_t)l * m + i] = T[(size_t)i * m + l] = spike[i];
+    }
+    for (int j = l; j < m; ++j) {
+      T[(size_t)j * m + j] = alpha[j];
+      if (j + 1 < m) T[(size_t)(j + 1) * m + j] = T[(size_t)j * m + (j + 1)] = betav[j];
+    }
+    jacobi_eig(m, T, w, Sm);
+    for (int i = 0; i < m; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return w[x] > w[y]; });     // p(sigma) = 1 on top
+    const double bm = betav[m - 1];
+    int nconv = 0, nin = 0;
+    for (int i = 0; i < m; ++i)
+      if (std::fabs(bm * Sm[(size_t)order[i] * m + (m - 1)]) <= tol_p) ++nconv; else break;
+    for (int i = 0; i < m; ++i) if (w[order[i]] > 2.0 * F.bound()) ++nin;
+    // thick restart: the converged pairs plus half of the rest, at least nev
+    int keep = std::max(nev, nconv + std::max(1, (m - nconv) / 2));
+    if (keep > m - 1) keep = m - 1;
+    std::vector<double> Ssel((size_t)2 * m * keep, 0.0);
+    theta.assign(keep, 0.0);
+    spike.assign(keep, 0.0);
+    for (int o = 0; o < keep; ++o) {
+      const int c = order[o];
+      theta[o] = w[c];
+      spike[o] = bm * Sm[(size_t)c * m + (m - 1)];
+      for (int j = 0; j < m; ++j) Ssel[2 * ((size_t)o * m + j)] = Sm[(size_t)c * m + j];
+    }
+    const double *sd = nullptr;
+    DNM_TRY(vec_upload_coefs(Ssel.data(), Ssel.size(), st, &sd));
+    DNM_TRY(vk_basis_update(V, n_local, m, keep, n_local, sd, st));
+    DNM_TRY(vk_copy(vecptr(V, n_local, keep), vecptr(V, n_local, m), n_local, st));
+    l = keep;
+    const bool last = its >= max_its;
+    if (debug)
+      fprintf(stderr, "dnm_eigsolve_interior: restart %d, %d pairs converged on the filter (tol %.1e), %d Ritz values in "
+              "the window, %d multiplies\n", its, nconv, tol_p, nin, ops.matvecs);
+    if (nconv >= nev || last) {
+      // Rayleigh-Ritz in H itself on the Ritz vectors of p(A) that have converged -- a nearly invariant subspace, so
+      // no spurious interior values -- which also separates the pairs sigma - d, sigma + d' that p nearly merges;
+      // then what the contract is about, |H u - theta u| <= tol |H|_inf, measured pair by pair, nearest first
+      F.on = false;
+      const int mv0 = ops.matvecs;
+      nrr = std::min(keep, std::max(nconv, nev));
+      std::vector<zc> Mh((size_t)nrr * nrr), col;
+      for (int j = 0; j < nrr; ++j) {
+        DNM_TRY(ops.mult(vecptr(V, n_local, j), F.ta));
+        DNM_TRY(ops.mdot(V, nrr, F.ta, col));
+        for (int i = 0; i < nrr; ++i) Mh[(size_t)i * nrr + j] = col[i];
+      }
+      for (int i = 0; i < nrr; ++i) {          // Hermitian part (the basis is orthonormal to rounding)
+        Mh[(size_t)i * nrr + i] = Mh[(size_t)i * nrr + i].real();
+        for (int j = i + 1; j < nrr; ++j) {
+          const zc v = 0.5 * (Mh[(size_t)i * nrr + j] + std::conj(Mh[(size_t)j * nrr + i]));
+          Mh[(size_t)i * nrr + j] = v;
+          Mh[(size_t)j * nrr + i] = std::conj(v);
+        }
+      }
+      std::vector<double> wh;
+      std::vector<zc> Qh;
+      hjacobi_eig(nrr, Mh, wh, Qh);
+      std::vector<int> oh(nrr);
+      for (int i = 0; i < nrr; ++i) oh[i] = i;
+      std::sort(oh.begin(), oh.end(), [&](int x, int y) { return std::fabs(wh[x] - target) < std::fabs(wh[y] - target); });
+      rth.assign(nrr, 0.0);
+      rQ.assign((size_t)nrr * nrr, zc(0));
+      for (int i = 0; i < nrr; ++i) {
+        rth[i] = wh[oh[i]];
+        for (int k = 0; k < nrr; ++k) rQ[(size_t)i * nrr + k] = Qh[(size_t)oh[i] * nrr + k];
+      }
+      nok = 0;
+      worst = 0.0;
+      double miss = 0.0;
+      for (int i = 0; i < std::min(nrr, nev_max); ++i) {
+        std::vector<zc> ci(rQ.begin() + (size_t)i * nrr, rQ.begin() + (size_t)(i + 1) * nrr);
+        DNM_TRY(vk_set(F.ta, n_local, 0.0, 0.0, st));
+        DNM_TRY(ops.maxpy(F.ta, V, nrr, ci));
+        DNM_TRY(ops.mult(F.ta, F.tb));
+        double n2 = 0;
+        DNM_TRY(vec_lanczos_update_host(F.tb, F.ta, nullptr, n_local, rth[i], 0.0, 0.0, &n2, st, 1.0));
+        DNM_TRY(ops.sum(&n2, 1));
+        const double res = std::sqrt(n2 > 0 ? n2 : 0.0) / nrmH;
+        if (res <= tol) { ++nok; worst = std::max(worst, res); }
+        else { miss = res; if (i < nev) worst = std::max(worst, res); break; }
+      }
+      extra_matvecs += ops.matvecs - mv0;
+      ops.matvecs = mv0;
+      F.on = true;
+      if (debug)
+        fprintf(stderr, "dnm_eigsolve_interior: restart %d, Rayleigh-Ritz in H on %d vectors, %d pairs pass "
+                "(largest residual / |H|_inf %.2e)\n", its, nrr, nok, worst);
+      if (nok >= nev || last) break;
+      // the filter's residuals were satisfied too early: ask for more, by what the measurement missed
+      tol_p *= std::max(1e-3, std::min(0.3, 0.3 * tol / std::max(miss, 1e-300)));
+      continue;
+    }
+    // Fewer than nev levels in the window, all of them found (after the first cycle the Ritz values inside the window
+    // are the well separated ones and converge first): widen it, keep the directions found so far as the new start
+    if (its >= 2 && nin < nev && nconv >= nin && widenings < 8) {
+      ++widenings;
+      const double hfull = std::max(target - emin, emax - target);
+      a = std::min(0.5 * hfull, a * std::min(2.0, std::max(1.25, (nev + 4.0) / std::max(nin, 1))));
+      DNM_TRY(plan());
+      std::vector<zc> ones(keep, zc(1.0 / std::sqrt((double)keep), 0.0));
+      DNM_TRY(vk_set(F.ta, n_local, 0.0, 0.0, st));
+      DNM_TRY(ops.maxpy(F.ta, V, keep, ones));
+      DNM_TRY(vk_copy(vecptr(V, n_local, 0), F.ta, n_local, st));
+      l = 0;
+      theta.clear();
+      spike.clear();
+      tol_p = tol;
+      if (debug) fprintf(stderr, "dnm_eigsolve_interior: window widened to %.4g, degree %d\n", a, F.d);
+    }
+  }
+
+  const int nout = std::min(nok, nev_max);
+  for (int i = 0; i < nout; ++i) evals[i] = rth[i];
+  if (evecs)
+    for (int i = 0; i < nout; ++i) {
+      void *dst = (char *)evecs + (size_t)i * (size_t)n_local * 16;
+      std::vector<zc> ci(rQ.begin() + (size_t)i * nrr, rQ.begin() + (size_t)(i + 1) * nrr);
+      DNM_TRY(vk_set(dst, n_local, 0.0, 0.0, st));
+      DNM_TRY(ops.maxpy(dst, V, nrr, ci));
+    }
+  if (debug)
+    fprintf(stderr, "dnm_eigsolve_interior: %d restarts, %d multiplies (+%d for Rayleigh-Ritz and the checks), degree %d, "
+            "half-width %.4g, largest residual / |H|_inf %.2e\n", its, ops.matvecs, extra_matvecs, F.d, a, worst);
+  DNM_HIP(hipStreamSynchronize(st));
+  stats->its = its;
+  stats->matvecs = ops.matvecs;
+  stats->nconv = nout;
+  stats->err_est = worst;
+  stats->reason = (nout >= nev) ? DNM_CONVERGED_TOL : DNM_DIVERGED_ITS;
   return 0;
 }
 

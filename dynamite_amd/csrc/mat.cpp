@@ -3,6 +3,7 @@
 // interfaces each entry point replaces.
 #include "mat.h"
 #include "vec_api.h"
+#include "row_fused.h"
 
 #include <algorithm>
 #include <cstring>
@@ -943,6 +944,7 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
             "null operator arrays");
   std::unique_ptr<dnm_mat> A(new dnm_mat());
   A->xparity = xparity != 0;
+  if (const char *e = knob("DNM_ROW_FUSE")) A->row_fuse = e[0] != '0';
   A->flags = flags;
   A->host_only = (flags & DNM_MAT_HOST_ONLY) != 0;
   const int64_t nterms = nmasks ? mask_offsets[nmasks] : 0;
@@ -1469,6 +1471,27 @@ int dnm_mat_local_part_bits(const dnm_mat *A, int *top_free_bit, int *gathers) {
   return 0;
 }
 
+// The handles whose one-rank multiply is a single launch of a one-thread-per-row kernel (launch_gather_matvec, or
+// launch_sc_matvec when the SpinConserve block kernel is off): Explicit / Auto, projections, SpinConserve in reference
+// order below the block kernel's sizes, XParity on those, Full / Parity under DNM_MAT_FORCE_GATHER.  Their fused twins
+// (row_fused_kernels.hip) take the recurrence's start vectors and the Lanczos sums.  DNM_ROW_FUSE=0 (experiments, read
+// when the handle is created): the multiply and separate sweeps, as before the twins existed -- the A/B switch of
+// profiles/interior_eigsolve.txt.
+static bool row_kernel_fuses(const dnm_mat *A) {
+  if (A->host_only || A->nranks != 1 || A->use_sc3 || !A->remote_passes.empty()) return false;
+  if (A->hypercube && A->plan.use_tiled) return false;
+  if (A->sc_pair && A->scblock.lb) return false;
+  return A->row_fuse;
+}
+
+static int launch_row_fused(dnm_mat *A, const void *x, void *y, const RowFuse &f, void *stream) {
+  const double *dg = A->have_diag ? (const double *)A->diag.p : nullptr;
+  if (A->sc_pair)
+    return launch_sc_matvec_fused(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, dg, x, y,
+                                  f, S(stream));
+  return launch_gather_matvec_fused(A->dmsc, A->left.dev, A->right.dev, A->M, dg, x, y, f, S(stream));
+}
+
 // y = A x - b z, <x, y> = sum conj(x_i) y_i and |y|^2 (z may be null).  When the plan is tiled, the first pass
 // starts its accumulators from -b z instead of zero and the last pass -- if it stages x in LDS -- accumulates the
 // sums (per-workgroup partials, summed by a second tiny kernel); otherwise one fused sweep does the same.
@@ -1491,6 +1514,21 @@ int dnm_mat_mult_lanczos(dnm_mat *A, const void *x, void *y, const void *z, doub
     DNM_TRY(launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, A->scblock, A->right.dev, A->m_local, A->row0, 0,
                             A->N, A->have_diag ? (const double *)A->diag.p : nullptr, x, y, S(stream), z, b, part));
     DNM_TRY(vk_reduce_partials(part, (int)nwg, 3, part + 3 * nwg, S(stream)));
+    DNM_HIP(hipMemcpyAsync(dot, part + 3 * nwg, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
+    DNM_HIP(hipStreamSynchronize(S(stream)));
+    return 0;
+  }
+  if (!tiled && row_kernel_fuses(A) && A->M == A->N && A->left.host.swz == A->right.host.swz) {
+    // one thread per row: the beta term joins the row's sum before the store, the sums leave as workgroup partials
+    const size_t nwg = (size_t)(A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local));
+    double *part = nullptr;
+    DNM_TRY(vec_scratch(((nwg + 1) * 3 + vk_reduce_scratch(3)) * sizeof(double), &part));
+    RowFuse f;
+    f.zinit = z;
+    f.zscale = b;
+    f.dot_out = part;
+    DNM_TRY(launch_row_fused(A, x, y, f, stream));
+    DNM_TRY(vk_reduce_partials(part, (int)nwg, 3, part + 3 * nwg, S(stream), part + 3 * nwg + 3));
     DNM_HIP(hipMemcpyAsync(dot, part + 3 * nwg, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
     DNM_HIP(hipStreamSynchronize(S(stream)));
     return 0;
@@ -1525,7 +1563,8 @@ int dnm_mat_fuses_init(const dnm_mat *A) {
   if (!A || A->host_only || !A->remote_passes.empty()) return 0;
   if (A->hypercube && A->plan.use_tiled && !A->local_passes.empty()) return 1;
   if (A->use_sc3) return 1;
-  return (A->sc_pair && A->scblock.lb && A->nranks == 1) ? 1 : 0;
+  if (A->sc_pair && A->scblock.lb && A->nranks == 1) return 1;
+  return row_kernel_fuses(A) ? 1 : 0;
 }
 
 // y = A x - b z + c z2 without the sums (Chebyshev / Clenshaw recurrences; z2 may be null): the extra terms ride
@@ -1556,6 +1595,15 @@ int dnm_mat_mult_sub2(dnm_mat *A, const void *x, void *y, const void *z, double 
     return launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, A->scblock, A->right.dev, A->m_local, A->row0, 0,
                            A->N, A->have_diag ? (const double *)A->diag.p : nullptr, x, y, S(stream), z, b, nullptr,
                            z2, c_re, c_im);
+  if (row_kernel_fuses(A)) {
+    RowFuse f;
+    f.zinit = z;
+    f.zscale = b;
+    f.zinit2 = z2;
+    f.z2re = c_re;
+    f.z2im = c_im;
+    return launch_row_fused(A, x, y, f, stream);
+  }
   DNM_TRY(dnm_mat_mult_local(A, x, y, stream));
   DNM_TRY(vk_axpby(y, z, A->m_local, -b, 0.0, 1.0, 0.0, S(stream)));
   if (z2) DNM_TRY(vk_axpby(y, z2, A->m_local, c_re, c_im, 1.0, 0.0, S(stream)));

@@ -89,6 +89,7 @@ struct dnm_mat {
   dnm::DevBuf d_scblock;          // block kernel: lb-bit patterns grouped by popcount
   dnm::DevBuf d_scperm;           // block kernel: optional block order
   dnm::ScBlock scblock{};         // lb == 0: block kernel not used
+  bool row_fuse = true;           // one-thread-per-row kernels with the fused epilogue (DNM_ROW_FUSE=0 at creation: off)
   int sc_nfast = 0;               // masks that are chain bonds with local signs
   // evolve: the Krylov step size at which the driver last handed over to the Chebyshev expansion (0: never) and
   // the basis size it belonged to -- later calls on this operator skip the Krylov probe when the estimate still holds

@@ -534,7 +534,8 @@ int dnm_mat_operator(const dnm_mat *A, int64_t *nmasks, int64_t *nterms, int64_t
                      int64_t *signs, double *coeffs);
 int dnm_comm_hooks(dnm_comm *c, dnm_mat *A, void *stream, dnm_hooks *out);
 
-enum { DNM_WHICH_LOWEST = 0, DNM_WHICH_HIGHEST = 1, DNM_WHICH_EXTERIOR = 2 };
+enum { DNM_WHICH_LOWEST = 0, DNM_WHICH_HIGHEST = 1, DNM_WHICH_EXTERIOR = 2,
+       DNM_WHICH_TARGET = 3 /* dnm_eigsolve_interior only: dnm_eigsolve takes the first three */ };
 
 /* Thick-restart Lanczos (SLEPc EPSKRYLOVSCHUR on a HEP).  evals: [nev_max]
  * doubles; evecs (optional, may be NULL): device buffer of nev_max vectors of
@@ -552,6 +553,33 @@ int dnm_eigsolve(dnm_mat *A, int64_t n_local, int nev, int which, double tol,
                  int ncv, int max_its, uint64_t seed, const dnm_hooks *hooks,
                  int nev_max, double *evals, void *evecs,
                  dnm_solver_stats *stats, void *stream);
+
+/* Eigenpairs of a Hermitian operator NEAREST `target` (SLEPc EPS_TARGET_MAGNITUDE), without a stored matrix and
+ * without a linear solve: thick-restart Lanczos on a Chebyshev filter of the folded spectrum,
+ *   p(A) = T_d(((A - target)^2 - c) / e) / T_d(-c / e)      (dnm_interior_filter_plan),
+ * each term of the recurrence two fused multiplies y = A x - b z + c2 z2 (dnm_mat_mult_sub2; through hooks->mult and
+ * one sweep per term when hooks are set), with a Rayleigh-Ritz step in A itself on the converged Ritz vectors.  The
+ * ends of the spectrum and the window's half-width (about nev + max(4, nev / 2) levels, from the density of states
+ * a Lanczos run estimates) are found by the call; the window is widened if it holds fewer than nev levels.
+ * Arguments as dnm_eigsolve (evals [nev_max], evecs optional: nev_max vectors of n_local complex128).  ncv <= 0 ->
+ * max(2*nev, nev+15) Lanczos vectors, ncv = -c: at most c vectors in all; the filter keeps three work vectors beside
+ * the ncv + 1 of the basis.  tol <= 0 -> 1e-8; max_its <= 0 -> 100 restarts.
+ * Convergence: |A u - theta u| <= tol * ||A||_inf, MEASURED for every returned pair (SLEPc EPS_CONV_NORM -- a
+ * criterion relative to theta means nothing at theta = 0, where mid-spectrum targets of traceless operators sit).
+ * Returns at least nev pairs when converged, ordered by |theta - target| ascending, eigenvectors orthonormal;
+ * stats->err_est = the largest measured residual / ||A||_inf, stats->matvecs = multiplies of the iteration (the
+ * Rayleigh-Ritz step and the checks are not counted), stats->its = restarts.  DESIGN.md section 5. */
+int dnm_eigsolve_interior(dnm_mat *A, int64_t n_local, int nev, double target, double tol,
+                          int ncv, int max_its, uint64_t seed, const dnm_hooks *hooks,
+                          int nev_max, double *evals, void *evecs,
+                          dnm_solver_stats *stats, void *stream);
+
+/* The parameters of that filter as pure arithmetic (host only).  With h = max(target - emin, emax - target):
+ * c = (h^2 + a^2) / 2, e = (h^2 - a^2) / 2, and *degree the smallest d >= 1 with T_d(c / e) >= damping, i.e.
+ * ceil(acosh(damping) / acosh(c / e)): |p| <= 1 / damping on every eigenvalue farther than a from the target,
+ * p(target) = 1.  Needs emax > emin, 0 < a < h, damping > 1. */
+int dnm_interior_filter_plan(double emin, double emax, double target, double a, double damping,
+                             int *degree, double *c, double *e);
 
 #ifdef __cplusplus
 }
