@@ -1692,6 +1692,76 @@ def _reduced_density_matrix(vec, subspace, keep):
     return rdm_partial(x, sub_c, keep)
 
 
+def rdm_sector_plan(sub_c, keep, xparity_sector=0):
+    """The blocks of a fixed-magnetisation state's reduced density matrix (``dnm_rdm_sector_plan``, host only): a list
+    of ``(n, rows, traced configurations)`` in ascending n and the scratch in bytes of a call computing all of them."""
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    nmax = keep.size + 1
+    nb, scratch = C.c_int(), C.c_size_t()
+    ns = (C.c_int32 * nmax)()
+    dims = np.zeros(nmax, dtype=np.int64)
+    traced = np.zeros(nmax, dtype=np.int64)
+    _lib.check(_lib.lib().dnm_rdm_sector_plan(C.byref(sub_c), keep.size, _lib.p64(keep), int(xparity_sector),
+                                              C.byref(nb), ns, _lib.p64(dims), _lib.p64(traced), C.byref(scratch)))
+    return [(int(ns[i]), int(dims[i]), int(traced[i])) for i in range(nb.value)], int(scratch.value)
+
+
+def _whole_state_on_rank0(vec, subspace):
+    """The state in reference order as one device tensor and a descriptor saying so, on rank 0; (None, None) on the
+    other ranks of a partitioned run (bpetsc_template_1.c:126-141 gathers likewise)."""
+    import torch
+    d = _dist()
+    sub_c = subspace['data']
+    if d is not None and d.get_world_size() > 1:
+        from . import _comm
+        if vec.internal:
+            sizes = [layout_partition(vec.sub_c, config.world_size, q)[3] for q in range(config.world_size)]
+        else:
+            sizes = [split_ownership(vec.size, config.world_size, q)[1] for q in range(config.world_size)]
+        parts = _comm.gather_varied(vec.local_natural(), sizes, dst=0)
+        if config.rank != 0:
+            return None, None
+        x = torch.cat(parts)
+    else:
+        x = vec.local_natural()
+    if int(sub_c.vec_swizzle) != 0:
+        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
+        sub_c.vec_swizzle = 0
+    return x.contiguous(), sub_c
+
+
+def rdm_sector_blocks(vec, subspace, keep, xparity_sector, sectors, plan=None, whole=None):
+    """``{n: device tensor (rows, rows) complex128}`` for the blocks ``sectors`` of the reduced density matrix of a
+    SpinConserve state (``xparity_sector`` = +-1: of the XParity half of it), computed in one launch sequence on rank 0;
+    None on the other ranks.  ``subspace`` is the SpinConserve descriptor (``_to_c()``); ``whole``: what
+    ``_whole_state_on_rank0`` returned for this state, for callers that take the blocks in several calls."""
+    import torch
+    config._initialize()
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    if plan is None:
+        plan = rdm_sector_plan(subspace['data'], keep, xparity_sector)[0]
+    rows = {n: dim for n, dim, _ in plan}
+    sectors = [int(n) for n in sectors]
+    for n in sectors:
+        if n not in rows:
+            raise ValueError('no block with %d up spins among the kept ones (feasible: %s)' % (n, sorted(rows)))
+    x, sub_c = whole if whole is not None else _whole_state_on_rank0(vec, subspace)
+    if x is None:
+        return None
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
+    expect = full.value // 2 if xparity_sector else full.value
+    if x.numel() != expect:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), expect))
+    out = {n: torch.empty((rows[n], rows[n]), dtype=torch.complex128, device=x.device) for n in sectors}
+    sel = (C.c_int32 * len(sectors))(*sectors)
+    ptrs = (C.c_void_p * len(sectors))(*[out[n].data_ptr() for n in sectors])
+    _lib.check(_lib.lib().dnm_rdm_sector_blocks(
+        C.c_void_p(x.data_ptr()), C.byref(sub_c), keep.size, _lib.p64(keep), int(xparity_sector), len(sectors), sel,
+        ptrs, _stream()))
+    return out
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -465,6 +465,16 @@ def reduced_density_matrix(state, keep):
     return _reduced_density_matrix(state, keep, on_device=False)
 
 
+def _check_keep(state, keep):
+    for n in range(1, keep.size):
+        if keep[n] <= keep[n - 1]:
+            raise ValueError('keep array must be strictly increasing')
+    if any(idx < 0 for idx in keep):
+        raise ValueError('spin index less than zero. keep: %s' % str(keep))
+    if any(idx >= state.L for idx in keep):
+        raise ValueError('spin index greater than spin chain length minus one. keep: %s' % str(keep))
+
+
 def _reduced_density_matrix(state, keep, on_device):
     """The argument checks of computations.py:294-349, then the kernel; ``on_device``: a device tensor on process 0
     and None elsewhere instead of the host array / ``[[-1]]``."""
@@ -477,13 +487,7 @@ def _reduced_density_matrix(state, keep, on_device):
     keep = np.array(keep, dtype=np.int64)
     if keep.size == 0:
         return np.array([[1]], dtype=np.complex128)
-    for n in range(1, keep.size):
-        if keep[n] <= keep[n - 1]:
-            raise ValueError('keep array must be strictly increasing')
-    if any(idx < 0 for idx in keep):
-        raise ValueError('spin index less than zero. keep: %s' % str(keep))
-    if any(idx >= state.L for idx in keep):
-        raise ValueError('spin index greater than spin chain length minus one. keep: %s' % str(keep))
+    _check_keep(state, keep)
     return backend.reduced_density_matrix(state.vec, state.subspace._to_c(), keep, on_device=on_device)
 
 
@@ -524,6 +528,113 @@ def _rdm_spectrum(state, keep):
     return torch.linalg.eigvalsh(rho).cpu().numpy()
 
 
+def _sector_subspace(state):
+    """(SpinConserve subspace, XParity sector or 0) when the state's reduced density matrices are direct sums over the
+    number of up spins kept -- a SpinConserve state, or an XParity state on top of one -- else None."""
+    from .subspaces import SpinConserve, XParity
+    sp = state.subspace
+    if type(sp) is SpinConserve:
+        return sp, 0
+    if type(sp) is XParity and type(sp.parent) is SpinConserve:
+        return sp.parent, int(sp.sector)
+    return None
+
+
+def reduced_density_matrix_sectors(state, keep, sectors=None, on_device=False):
+    """The reduced density matrix of a fixed-magnetisation state block by block: ``{n: rho_n}``, n the number of set
+    bits (down spins, as SpinConserve counts them) among the kept spins.  ``rho_n`` couples the kept configurations
+    with n set bits in ascending integer order -- it is ``rho[idx][:, idx]`` of the dense matrix, ``idx`` the indices
+    of popcount n, and all entries of the dense matrix outside the blocks are zero.  Only the blocks are computed (by
+    kernels that never touch a product state outside the subspace), so cuts of more than 15 spins are possible as
+    long as the blocks fit the device.
+
+    ``state`` lives on ``SpinConserve`` or on ``XParity(SpinConserve)``; any other subspace raises ValueError.
+    ``sectors``: the n wanted (default: every feasible one, max(0, k - (L - len(keep))) <= n <= min(k, len(keep))).
+    Blocks are numpy arrays, or device tensors with ``on_device``; on the other processes of a partitioned run every
+    block is ``[[-1]]`` (None with ``on_device``), as for ``reduced_density_matrix``."""
+    from . import backend
+    state.assert_initialized()
+    config._initialize()
+    route = _sector_subspace(state)
+    if route is None:
+        raise ValueError('sector-resolved reduced density matrices need a SpinConserve state or an XParity state on '
+                         'top of SpinConserve, not %r' % (state.subspace,))
+    sub, xsec = route
+    keep = np.array(keep, dtype=np.int64).reshape(-1)
+    _check_keep(state, keep)
+    if keep.size == 0:
+        if sectors is not None and [int(n) for n in sectors] != [0]:
+            raise ValueError('no kept spins: the only block is n = 0')
+        return {0: np.array([[1]], dtype=np.complex128)}
+    sub_c = state.subspace._to_c() if xsec == 0 else sub._to_c()
+    plan = backend.rdm_sector_plan(sub_c['data'], keep, xsec)[0]
+    if sectors is None:
+        sectors = [n for n, _, _ in plan]
+    sectors = [int(n) for n in sectors]
+    blocks = backend.rdm_sector_blocks(state.vec, sub_c, keep, xsec, sectors, plan=plan)
+    if blocks is None:
+        return {n: (None if on_device else np.array([[-1]], dtype=np.complex128)) for n in sectors}
+    return blocks if on_device else {n: b.cpu().numpy() for n, b in blocks.items()}
+
+
+def _sector_spectrum(state, keep):
+    """Eigenvalues of the reduced density matrix through its blocks, one block at a time: compute, diagonalise on the
+    device, free -- the peak is the largest block plus the solver's workspace.  An XParity state's blocks n and
+    len(keep) - n have the same spectrum (the global flip maps one onto the other): the lower half is computed and
+    counted twice.  numpy array, ascending, on process 0; None elsewhere."""
+    import torch
+    from . import backend
+    state.assert_initialized()
+    config._initialize()
+    sub, xsec = _sector_subspace(state)
+    keep = np.array(keep, dtype=np.int64).reshape(-1)
+    _check_keep(state, keep)
+    if keep.size == 0:
+        return np.array([1.0])
+    sub_c = state.subspace._to_c() if xsec == 0 else sub._to_c()
+    plan = backend.rdm_sector_plan(sub_c['data'], keep, xsec)[0]
+    whole = backend._whole_state_on_rank0(state.vec, sub_c)      # (reference order: gathered / copied once)
+    if whole[0] is None:
+        return None
+    out = []
+    for n, _, _ in plan:
+        if xsec and 2 * n > keep.size:
+            continue
+        blocks = backend.rdm_sector_blocks(state.vec, sub_c, keep, xsec, [n], plan=plan, whole=whole)
+        w = torch.linalg.eigvalsh(blocks.pop(n)).cpu().numpy()
+        out.append(w)
+        if xsec and 2 * n != keep.size:
+            out.append(w)
+    return np.sort(np.concatenate(out))
+
+
+def _takes_sector_route(state, keep):
+    """Where the entropies go through the blocks: the cases the dense form cannot do -- XParity(SpinConserve) states
+    (no dense form exists for them) and SpinConserve states with more than 15 spins kept.  Smaller SpinConserve cuts
+    stay on the dense route (_rdm_spectrum) until the two are timed against each other at 13 of 26 spins
+    (tools/rdm_sectors_timing.py); entanglement_spectrum takes the blocks at every size."""
+    route = _sector_subspace(state)
+    if route is None:
+        return False
+    return route[1] != 0 or len(keep) > 15
+
+
+def _spectrum(state, keep):
+    if _takes_sector_route(state, keep):
+        return _sector_spectrum(state, keep)
+    return _rdm_spectrum(state, keep)
+
+
+def entanglement_spectrum(state, keep):
+    """All eigenvalues of the reduced density matrix of ``state`` on the spins ``keep``, ascending (numpy array; None
+    on the processes other than 0).  SpinConserve and XParity(SpinConserve) states go block by block through
+    ``reduced_density_matrix_sectors``' kernels, whatever the size of the cut; every other state through the dense
+    matrix."""
+    if _sector_subspace(state) is not None:
+        return _sector_spectrum(state, keep)
+    return _rdm_spectrum(state, keep)
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)
@@ -532,7 +643,7 @@ def _entropy_of_spectrum(w):
 
 def entanglement_entropy(state, keep):
     """Bipartite entanglement entropy across the cut keep | rest (computations.py:351-383)."""
-    w = _rdm_spectrum(state, keep)
+    w = _spectrum(state, keep)
     if w is None:                # everything is computed on process 0
         return -1
     return _entropy_of_spectrum(w)
@@ -546,7 +657,7 @@ def dm_entanglement_entropy(dm):
 def renyi_entropy(state, keep, alpha, method='eigsolve'):
     """Renyi entropy of the reduced density matrix (computations.py:410-454)."""
     if method == 'eigsolve' or alpha in (0, 1, 'inf'):
-        w = _rdm_spectrum(state, keep)
+        w = _spectrum(state, keep)
         if w is None:
             return -1
         return _renyi_of_spectrum(w, alpha)

@@ -125,6 +125,28 @@ void rdm_plan(const RdmGeom &geo, int *logtm, int *ntiles, int *nsplit, int64_t 
               size_t *partial_bytes);
 // rho (2^k x 2^k complex128, row-major) from the state x on `sub`; partial: scratch of rdm_plan's size
 int launch_rdm(const void *x, const SubView &sub, const RdmGeom &geo, void *partial, void *rho, hipStream_t st);
+// the fan-in-32 tree of the slice sum on its own: partial holds *nsplit slices of nelem amplitudes (and room for the
+// intermediate levels behind them, as rdm_plan sizes it); on return *level holds *nsplit <= 32 slices still to be added
+int rdm_sum_slices(void *partial, int64_t nelem, int *nsplit, void **level, hipStream_t st);
+
+// Sector-resolved form for SpinConserve states (rdm_sector_kernels.hip): block n of the reduced density matrix couples
+// the kept configurations with n set bits.  RdmGeom::k / L: kept spins / all spins, segments as above.
+struct RdmSectorBlock {
+  int32_t n, m;               // set bits among the kept / the traced spins (n + m = the subspace's k)
+  int64_t dim, traced;        // C(kept, n) rows, C(L - kept, m) traced configurations
+  int64_t per_slice;          // traced configurations per slice (rdm_sector_plan)
+  void *out;                  // dim x dim complex128, row-major (device)
+};
+struct RdmSectorTile {
+  int32_t blk, ti, tj, pad;   // 64 x 64 tile (ti, tj), tj <= ti, of block blk
+};
+// slices for the blocks of one launch (fills per_slice) and the scratch: table_bytes + partial_bytes
+int rdm_sector_plan(int nblocks, RdmSectorBlock *blocks, int64_t *ntiles, int *nsplit, size_t *table_bytes,
+                    size_t *partial_bytes);
+// contig: the kept spins are [0, k); xparity_sector: 0, or +-1 for a state on the XParity half (x: the representatives)
+int launch_rdm_sector(const void *x, const SubView &sub, const RdmGeom &geo, bool contig, int xparity_sector,
+                      int nblocks, const RdmSectorBlock *blocks, int64_t ntiles, int nsplit, size_t table_bytes,
+                      void *scratch, hipStream_t st);
 
 // ---- vector kernels ---------------------------------------------------------
 int vk_set(void *x, int64_t n, double re, double im, hipStream_t st);

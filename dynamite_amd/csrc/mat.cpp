@@ -789,6 +789,29 @@ int rdm_release_scratch() {
 }  // namespace dnm
 extern "C" {
 
+// runs of kept / traced spin positions (kernels.h: RdmGeom)
+static void rdm_geom(int L, int keep_size, const int64_t *keep, RdmGeom *out) {
+  RdmGeom &geo = *out;
+  memset(&geo, 0, sizeof(geo));
+  geo.k = keep_size;
+  geo.L = L;
+  uint64_t keepmask = 0;
+  for (int i = 0; i < keep_size; ++i) keepmask |= (uint64_t)1 << keep[i];
+  for (int pos = 0; pos < L;) {
+    const bool kept = (keepmask >> pos) & 1;
+    int end = pos;
+    while (end < L && (((keepmask >> end) & 1) != 0) == kept) ++end;
+    if (kept) {
+      geo.klen[geo.nseg_keep] = (int8_t)(end - pos);
+      geo.kpos[geo.nseg_keep++] = (int8_t)pos;
+    } else {
+      geo.tlen[geo.nseg_tr] = (int8_t)(end - pos);
+      geo.tpos[geo.nseg_tr++] = (int8_t)pos;
+    }
+    pos = end;
+  }
+}
+
 int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
                                void *rho, void *stream) {
   DNM_CHECK(x && sub && rho && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
@@ -803,24 +826,7 @@ int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_
     DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
   }
   RdmGeom geo;
-  memset(&geo, 0, sizeof(geo));
-  geo.k = keep_size;
-  geo.L = L;
-  uint64_t keepmask = 0;
-  for (int i = 0; i < keep_size; ++i) keepmask |= (uint64_t)1 << keep[i];
-  for (int pos = 0; pos < L;) {     // runs of kept / traced positions
-    const bool kept = (keepmask >> pos) & 1;
-    int end = pos;
-    while (end < L && (((keepmask >> end) & 1) != 0) == kept) ++end;
-    if (kept) {
-      geo.klen[geo.nseg_keep] = (int8_t)(end - pos);
-      geo.kpos[geo.nseg_keep++] = (int8_t)pos;
-    } else {
-      geo.tlen[geo.nseg_tr] = (int8_t)(end - pos);
-      geo.tpos[geo.nseg_tr++] = (int8_t)pos;
-    }
-    pos = end;
-  }
+  rdm_geom(L, keep_size, keep, &geo);
   int logtm, ntiles, nsplit;
   int64_t cps;
   size_t pbytes;
@@ -841,6 +847,115 @@ int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_
   }
   DNM_TRY(launch_rdm(x, s.dev, geo, scratch, rho, S(stream)));
   DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` is released on return
+  return 0;
+}
+
+// ---- sector-resolved reduced density matrix (SpinConserve, XParity over SpinConserve) ------------------------------
+// argument checks and the list of feasible blocks, on the host
+static int rdm_sector_blocks_of(const dnm_subspace *sub, int keep_size, const int64_t *keep, int xparity_sector,
+                                SubView *view, RdmGeom *geo, bool *contig, std::vector<RdmSectorBlock> *blocks) {
+  DNM_CHECK(sub && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
+  SubView v{};
+  DNM_TRY(view_from_c(sub, &v));
+  DNM_CHECK(v.type == DNM_SPIN_CONSERVE, "sector-resolved reduced density matrices need a SpinConserve subspace "
+            "(type %d given)", v.type);
+  const int L = v.L, k = v.k;
+  DNM_CHECK(xparity_sector == 0 || xparity_sector == 1 || xparity_sector == -1, "xparity_sector must be 0, +1 or -1");
+  DNM_CHECK(xparity_sector == 0 || L == 2 * k, "XParity needs SpinConserve(L, L/2): L=%d, k=%d", L, k);
+  DNM_CHECK(keep_size <= L, "more kept spins than spins");
+  DNM_CHECK(keep_size <= 40, "reduced density matrix blocks of %d kept spins: at most 40", keep_size);
+  bool low = keep_size < L;
+  for (int i = 0; i < keep_size; ++i) {
+    DNM_CHECK(keep[i] >= 0 && keep[i] < L, "kept spin index %lld out of range [0, %d)", (long long)keep[i], L);
+    DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
+    low = low && keep[i] == i;
+  }
+  rdm_geom(L, keep_size, keep, geo);
+  *contig = low;
+  *view = v;
+  blocks->clear();
+  const int nlo = std::max(0, k - (L - keep_size)), nhi = std::min(k, keep_size);
+  for (int n = nlo; n <= nhi; ++n) {
+    RdmSectorBlock b{};
+    b.n = n;
+    b.m = k - n;
+    b.dim = v.nchoosek[(int64_t)n * v.ld + keep_size];
+    b.traced = v.nchoosek[(int64_t)(k - n) * v.ld + (L - keep_size)];
+    DNM_CHECK(b.dim >= 1 && b.dim < ((int64_t)1 << 31), "block n=%d of the reduced density matrix has %lld rows: "
+              "2^31 or more", n, (long long)b.dim);
+    blocks->push_back(b);
+  }
+  return 0;
+}
+
+int dnm_rdm_sector_plan(const dnm_subspace *sub, int keep_size, const int64_t *keep, int xparity_sector, int *nblocks,
+                        int32_t *n_of_block, int64_t *dim_of_block, int64_t *traced_of_block,
+                        size_t *scratch_bytes_max) {
+  DNM_CHECK(nblocks, "null argument");
+  SubView v{};
+  RdmGeom geo;
+  bool contig;
+  std::vector<RdmSectorBlock> blocks;
+  DNM_TRY(rdm_sector_blocks_of(sub, keep_size, keep, xparity_sector, &v, &geo, &contig, &blocks));
+  *nblocks = (int)blocks.size();
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    if (n_of_block) n_of_block[i] = blocks[i].n;
+    if (dim_of_block) dim_of_block[i] = blocks[i].dim;
+    if (traced_of_block) traced_of_block[i] = blocks[i].traced;
+  }
+  if (scratch_bytes_max) {
+    int64_t nt;
+    int ns;
+    size_t tb, pb;
+    DNM_TRY(rdm_sector_plan((int)blocks.size(), blocks.data(), &nt, &ns, &tb, &pb));
+    *scratch_bytes_max = tb + pb;
+  }
+  return 0;
+}
+
+int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
+                          int xparity_sector, int nsel, const int32_t *sel_n, void *const *out_ptrs, void *stream) {
+  DNM_CHECK(x && nsel >= 1 && sel_n && out_ptrs, "null argument");
+  SubView v{};
+  RdmGeom geo;
+  bool contig;
+  std::vector<RdmSectorBlock> all, blocks;
+  DNM_TRY(rdm_sector_blocks_of(sub, keep_size, keep, xparity_sector, &v, &geo, &contig, &all));
+  DNM_CHECK(v.sc3 == 0, "the sector kernels read the state in reference order (vec_swizzle %d given)", v.sc3);
+  for (int i = 0; i < nsel; ++i) {
+    const int n = sel_n[i] - all.front().n;
+    DNM_CHECK(n >= 0 && n < (int)all.size(), "no block with %d set bits among the kept spins (feasible: %d..%d)",
+              (int)sel_n[i], all.front().n, all.back().n);
+    DNM_CHECK(out_ptrs[i], "null output for block n=%d", (int)sel_n[i]);
+    blocks.push_back(all[(size_t)n]);
+    blocks.back().out = out_ptrs[i];
+  }
+  int64_t ntiles;
+  int nsplit;
+  size_t tbytes, pbytes;
+  DNM_TRY(rdm_sector_plan((int)blocks.size(), blocks.data(), &ntiles, &nsplit, &tbytes, &pbytes));
+  const size_t bytes = tbytes + pbytes;
+  SubOwned s;
+  DNM_TRY(s.init(sub, true));
+  // scratch by the policy of the dense form: small ones are kept between calls
+  DevBuf &cached = g_rdm_scratch;
+  DevBuf big;
+  void *scratch = nullptr;
+  if (bytes <= ((size_t)1 << 30) && cached.bytes >= bytes) {
+    scratch = cached.p;
+  } else {
+    if (bytes <= ((size_t)1 << 30)) cached.release();
+    size_t free_b = 0, total_b = 0;
+    DNM_HIP(hipMemGetInfo(&free_b, &total_b));
+    DNM_CHECK(bytes <= free_b, "reduced density matrix blocks: %zu bytes of scratch asked for (%lld tiles of 64 x 64 in "
+              "%d slices), %zu bytes of device memory free", bytes, (long long)ntiles, nsplit, free_b);
+    DevBuf &dst = bytes <= ((size_t)1 << 30) ? cached : big;
+    DNM_TRY(dst.alloc(bytes));
+    scratch = dst.p;
+  }
+  DNM_TRY(launch_rdm_sector(x, s.dev, geo, contig, xparity_sector, (int)blocks.size(), blocks.data(), ntiles, nsplit,
+                            tbytes, scratch, S(stream)));
+  DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` and the subspace tables are released on return
   return 0;
 }
 

@@ -464,6 +464,23 @@ static int rdm_launch(const c128 *x, const SubView &sub, const RdmGeom &geo, int
   return 0;
 }
 
+int rdm_sum_slices(void *partial, int64_t nelem, int *nsplit, void **level, hipStream_t st) {
+  c128 *cur = (c128 *)partial, *nxt = cur + (int64_t)*nsplit * nelem;
+  int ns = *nsplit;
+  while (ns > RDM_FAN) {
+    const int nout = (ns + RDM_FAN - 1) / RDM_FAN;
+    hipLaunchKernelGGL(rdm_reduce_kernel, dim3((unsigned)((nelem + RDM_NT - 1) / RDM_NT), (unsigned)nout),
+                       dim3(RDM_NT), 0, st, cur, nxt, nelem, ns);
+    cur = nxt;
+    nxt = cur + (int64_t)nout * nelem;
+    ns = nout;
+  }
+  DNM_HIP(hipGetLastError());
+  *nsplit = ns;
+  *level = cur;
+  return 0;
+}
+
 template <int ST>
 static int rdm_dispatch_tm(int logtm, const c128 *x, const SubView &sub, const RdmGeom &geo, int ntiles, int nsplit,
                            int64_t cps, c128 *partial, c128 *rho, hipStream_t st) {

@@ -259,6 +259,11 @@ class State:
         from . import computations
         return computations.entanglement_entropy(self, keep)
 
+    def entanglement_spectrum(self, keep):
+        """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
+        from . import computations
+        return computations.entanglement_spectrum(self, keep)
+
     # ------------------------------------------------------------------ BLAS-1
     def dot(self, x):
         self.assert_initialized()

@@ -180,6 +180,21 @@ int dnm_check_conserves(int64_t nmasks, const int64_t *masks, const int64_t *mas
  * complex128, row-major, bit i of a row/column index = spin keep[i]. */
 int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size,
                                const int64_t *keep, void *rho, void *stream);
+/* The same matrix block by block, for a state of fixed magnetisation: sub is SpinConserve(L, k) and x either the
+ * whole state (xparity_sector = 0) or its XParity half of sector +-1 (the dim / 2 representatives; L = 2 k), in
+ * reference order.  Block n couples the kept configurations with n set bits, max(0, k - (L - keep_size)) <= n <=
+ * min(k, keep_size), in ascending order: it is rho[idx][:, idx] of the dense matrix, idx = the row indices of
+ * popcount n.  keep_size <= 40 and every block below 2^31 rows.
+ * dnm_rdm_sector_plan (host only, no device needed): the feasible blocks -- their n, rows and numbers of traced
+ * configurations (arrays of min(k, keep_size) + 1 entries suffice; any may be null) -- and the scratch in bytes that
+ * a call computing all of them at once takes.
+ * dnm_rdm_sector_blocks: the blocks sel_n[0..nsel) in one launch sequence, block i into out_ptrs[i] (device,
+ * rows x rows complex128, row-major).  Blocks are Hermitian to the last bit, with real diagonals. */
+int dnm_rdm_sector_plan(const dnm_subspace *sub, int keep_size, const int64_t *keep, int xparity_sector,
+                        int *nblocks, int32_t *n_of_block, int64_t *dim_of_block, int64_t *traced_of_block,
+                        size_t *scratch_bytes_max);
+int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
+                          int xparity_sector, int nsel, const int32_t *sel_n, void *const *out_ptrs, void *stream);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
