@@ -1658,12 +1658,10 @@ def reduced_density_matrix(vec, subspace, keep, on_device=False):
 
 def _reduced_density_matrix(vec, subspace, keep):
     """The reduced density matrix as a flat device tensor on rank 0, None on the other ranks."""
-    import torch
     config._initialize()
     keep = np.ascontiguousarray(keep, dtype=np.int64)
     d = _dist()
     x = vec.array
-    K = 1 << keep.size
     if d is not None and d.get_world_size() > 1:
         blk = rdm_block_subspace(subspace, config.rank, config.world_size, keep)
         if blk is not None:
@@ -1671,18 +1669,8 @@ def _reduced_density_matrix(vec, subspace, keep):
             rho = rdm_partial(x, blk, keep)
             _comm.reduce_sum(rho, dst=0)
             return rho if config.rank == 0 else None
-        from . import _comm
-        if vec.internal:
-            sizes = [layout_partition(vec.sub_c, config.world_size, q)[3] for q in range(config.world_size)]
-        else:
-            sizes = [split_ownership(vec.size, config.world_size, q)[1] for q in range(config.world_size)]
-        parts = _comm.gather_varied(vec.local_natural(), sizes, dst=0)
-        if config.rank != 0:
-            return None
-        x = torch.cat(parts)                 # the whole state in index order
-        sub_c = _lib.Subspace.from_buffer_copy(subspace['data'])
-        sub_c.vec_swizzle = 0
-        return rdm_partial(x, sub_c, keep)
+        x, sub_c = _whole_state_on_rank0(vec, subspace)
+        return None if x is None else rdm_partial(x, sub_c, keep)
     sub_c = subspace['data']
     if vec.internal:
         # the kernel gathers by reference index: hand it the state in that order

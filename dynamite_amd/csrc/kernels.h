@@ -126,7 +126,9 @@ void rdm_plan(const RdmGeom &geo, int *logtm, int *ntiles, int *nsplit, int64_t 
 // rho (2^k x 2^k complex128, row-major) from the state x on `sub`; partial: scratch of rdm_plan's size
 int launch_rdm(const void *x, const SubView &sub, const RdmGeom &geo, void *partial, void *rho, hipStream_t st);
 // the fan-in-32 tree of the slice sum on its own: partial holds *nsplit slices of nelem amplitudes (and room for the
-// intermediate levels behind them, as rdm_plan sizes it); on return *level holds *nsplit <= 32 slices still to be added
+// intermediate levels behind them: rdm_partial_bytes in all); on return *level holds *nsplit <= 32 slices still to be
+// added
+size_t rdm_partial_bytes(int64_t nsplit, int64_t nelem);
 int rdm_sum_slices(void *partial, int64_t nelem, int *nsplit, void **level, hipStream_t st);
 
 // Sector-resolved form for SpinConserve states (rdm_sector_kernels.hip): block n of the reduced density matrix couples

@@ -812,39 +812,53 @@ static void rdm_geom(int L, int keep_size, const int64_t *keep, RdmGeom *out) {
   }
 }
 
+// the kept spins of a call: at most `cap` of them (over_cap: the caller's message, a format that is handed keep_size
+// twice and may use it once), inside [0, L), strictly increasing (bpetsc_template_1.c:117-121)
+static int rdm_check_keep(int L, int keep_size, const int64_t *keep, int cap, const char *over_cap) {
+  DNM_CHECK(keep_size <= L, "more kept spins than spins");
+  DNM_CHECK(keep_size <= cap, over_cap, keep_size, keep_size);
+  for (int i = 0; i < keep_size; ++i) {
+    DNM_CHECK(keep[i] >= 0 && keep[i] < L, "kept spin index %lld out of range [0, %d)", (long long)keep[i], L);
+    DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
+  }
+  return 0;
+}
+
+// Scratch for the partial tiles: up to 1 GiB it is kept between calls (hipMalloc costs more than the kernel), a larger
+// one lives in `big`, which the caller releases after the stream has drained.  `what`, tiles, tm, slices: for the
+// message when the device has no room.
+static int rdm_scratch(size_t bytes, DevBuf *big, void **scratch, const char *what, long long tiles, int tm,
+                       int slices) {
+  DevBuf &cached = g_rdm_scratch;
+  const bool keep_it = bytes <= ((size_t)1 << 30);
+  if (!keep_it || cached.bytes < bytes) {
+    if (keep_it) cached.release();
+    size_t free_b = 0, total_b = 0;
+    DNM_HIP(hipMemGetInfo(&free_b, &total_b));
+    DNM_CHECK(bytes <= free_b, "%s: %zu bytes of scratch asked for (%lld tiles of %d x %d in %d slices), %zu bytes of "
+              "device memory free", what, bytes, tiles, tm, tm, slices, free_b);
+    DNM_TRY((keep_it ? cached : *big).alloc(bytes));
+  }
+  *scratch = keep_it ? cached.p : big->p;
+  return 0;
+}
+
 int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
                                void *rho, void *stream) {
   DNM_CHECK(x && sub && rho && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
   SubOwned s;
   DNM_TRY(s.init(sub, true));
   const int L = s.host.L;
-  DNM_CHECK(keep_size <= L, "more kept spins than spins");
-  DNM_CHECK(keep_size <= 15, "reduced density matrix of %d spins (4^%d entries) is too large", keep_size, keep_size);
-  for (int i = 0; i < keep_size; ++i) {
-    DNM_CHECK(keep[i] >= 0 && keep[i] < L, "kept spin index %lld out of range [0, %d)", (long long)keep[i], L);
-    // bpetsc_template_1.c:117-121
-    DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
-  }
+  DNM_TRY(rdm_check_keep(L, keep_size, keep, 15, "reduced density matrix of %d spins (4^%d entries) is too large"));
   RdmGeom geo;
   rdm_geom(L, keep_size, keep, &geo);
   int logtm, ntiles, nsplit;
   int64_t cps;
   size_t pbytes;
   rdm_plan(geo, &logtm, &ntiles, &nsplit, &cps, &pbytes);
-  // scratch for the partial tiles: small ones are kept between calls (hipMalloc costs more than the kernel)
-  DevBuf &cached = g_rdm_scratch;
   DevBuf big;
   void *scratch = nullptr;
-  if (pbytes <= ((size_t)1 << 30)) {
-    if (cached.bytes < pbytes) {
-      cached.release();
-      DNM_TRY(cached.alloc(pbytes));
-    }
-    scratch = cached.p;
-  } else {
-    DNM_TRY(big.alloc(pbytes));
-    scratch = big.p;
-  }
+  DNM_TRY(rdm_scratch(pbytes, &big, &scratch, "reduced density matrix", ntiles, 1 << logtm, nsplit));
   DNM_TRY(launch_rdm(x, s.dev, geo, scratch, rho, S(stream)));
   DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` is released on return
   return 0;
@@ -862,16 +876,10 @@ static int rdm_sector_blocks_of(const dnm_subspace *sub, int keep_size, const in
   const int L = v.L, k = v.k;
   DNM_CHECK(xparity_sector == 0 || xparity_sector == 1 || xparity_sector == -1, "xparity_sector must be 0, +1 or -1");
   DNM_CHECK(xparity_sector == 0 || L == 2 * k, "XParity needs SpinConserve(L, L/2): L=%d, k=%d", L, k);
-  DNM_CHECK(keep_size <= L, "more kept spins than spins");
-  DNM_CHECK(keep_size <= 40, "reduced density matrix blocks of %d kept spins: at most 40", keep_size);
-  bool low = keep_size < L;
-  for (int i = 0; i < keep_size; ++i) {
-    DNM_CHECK(keep[i] >= 0 && keep[i] < L, "kept spin index %lld out of range [0, %d)", (long long)keep[i], L);
-    DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
-    low = low && keep[i] == i;
-  }
+  DNM_TRY(rdm_check_keep(L, keep_size, keep, 40, "reduced density matrix blocks of %d kept spins: at most 40"));
   rdm_geom(L, keep_size, keep, geo);
-  *contig = low;
+  // the kept spins are [0, keep_size): increasing from 0 and ending at keep_size - 1
+  *contig = keep_size < L && (keep_size == 0 || keep[keep_size - 1] == keep_size - 1);
   *view = v;
   blocks->clear();
   const int nlo = std::max(0, k - (L - keep_size)), nhi = std::min(k, keep_size);
@@ -937,22 +945,9 @@ int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size,
   const size_t bytes = tbytes + pbytes;
   SubOwned s;
   DNM_TRY(s.init(sub, true));
-  // scratch by the policy of the dense form: small ones are kept between calls
-  DevBuf &cached = g_rdm_scratch;
   DevBuf big;
   void *scratch = nullptr;
-  if (bytes <= ((size_t)1 << 30) && cached.bytes >= bytes) {
-    scratch = cached.p;
-  } else {
-    if (bytes <= ((size_t)1 << 30)) cached.release();
-    size_t free_b = 0, total_b = 0;
-    DNM_HIP(hipMemGetInfo(&free_b, &total_b));
-    DNM_CHECK(bytes <= free_b, "reduced density matrix blocks: %zu bytes of scratch asked for (%lld tiles of 64 x 64 in "
-              "%d slices), %zu bytes of device memory free", bytes, (long long)ntiles, nsplit, free_b);
-    DevBuf &dst = bytes <= ((size_t)1 << 30) ? cached : big;
-    DNM_TRY(dst.alloc(bytes));
-    scratch = dst.p;
-  }
+  DNM_TRY(rdm_scratch(bytes, &big, &scratch, "reduced density matrix blocks", (long long)ntiles, 64, nsplit));
   DNM_TRY(launch_rdm_sector(x, s.dev, geo, contig, xparity_sector, (int)blocks.size(), blocks.data(), ntiles, nsplit,
                             tbytes, scratch, S(stream)));
   DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` and the subspace tables are released on return

@@ -10,28 +10,16 @@
 // split the traced index among themselves and combine at the end (wave shuffles, then LDS).
 // Partial tiles go to a scratch buffer and a second kernel sums the slices and mirrors the
 // upper triangle, so the result is deterministic (no atomics).
-#include "kernels.h"
+#include "rdm_tile.h"
 
 namespace dnm {
 
-typedef double2 c128;
-
-constexpr int RDM_NT = 256;
 constexpr int RDM_STAGE = 1024;   // amplitudes per operand per chunk
 
 template <int ST>
 __device__ __forceinline__ c128 rdm_fetch(const c128 *__restrict__ x, uint64_t state, const SubView &sub) {
   const int64_t idx = Sub<ST>::s2i((int64_t)state, sub);
   return idx >= 0 ? x[vec_pos(idx, sub.swz)] : make_double2(0.0, 0.0);
-}
-
-__device__ __forceinline__ uint64_t rdm_deposit(uint64_t v, const int8_t *len, const int8_t *pos, int nseg) {
-  uint64_t out = 0;
-  for (int i = 0; i < nseg; ++i) {
-    out |= (v & (((uint64_t)1 << len[i]) - 1)) << pos[i];
-    v >>= len[i];
-  }
-  return out;
 }
 
 template <int ST, int LOGTM>
@@ -48,12 +36,9 @@ rdm_tile_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo
   __shared__ uint64_t pa[TM], pb[TM];
 
   const int tid = threadIdx.x;
-  // tile (ti, tj), tj <= ti, from the linear lower-triangle index
   const int tile = blockIdx.x;
-  int ti = (int)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-  while ((int64_t)(ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-  while ((int64_t)ti * (ti + 1) / 2 > tile) --ti;
-  const int tj = tile - (int)((int64_t)ti * (ti + 1) / 2);
+  int ti, tj;
+  rdm_tile_coords(tile, &ti, &tj);
   const bool diag_tile = ti == tj;
   const int64_t K = (int64_t)1 << geo.k, T = (int64_t)1 << (geo.L - geo.k);
   const int64_t a0 = (int64_t)ti * TM, b0 = (int64_t)tj * TM;
@@ -245,29 +230,13 @@ rdm_small_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom ge
 }
 
 // ---- 64 x 64 tiles on the matrix cores (k >= 6) ------------------------------------------------------------
-// The same tile, slices and scratch as rdm_tile_kernel<ST, 6>, with the rank-T update done by
-// v_mfma_f64_16x16x4_f64: a wavefront owns a 32 x 32 block of the tile (2 x 2 MFMA blocks, real and imaginary
-// accumulators: 64 VGPRs) and per four traced configurations reads two A and two B fragments from LDS -- each lane one
-// complex amplitude (ds_read_b128: row / column = lane & 15, traced slot = lane >> 4) -- where the VALU form reads
-// eight amplitudes per 16 complex products: an eighth of the LDS traffic per flop, and the FMAs leave the vector unit.
-//   rho = A B^H:  Re += Ar Br^T + Ai Bi^T,   Im += Ai Br^T + (-Ar) Bi^T      (four real MFMAs per complex block)
-// C/D layout of the f64 MFMA (not the f32 one): col = lane & 15, row = (lane >> 4) + 4 * reg.
-// The next chunk's amplitudes are gathered into registers while the matrix cores work on the staged one.
-typedef double mfma_acc __attribute__((ext_vector_type(4)));
-
-// waves per SIMD the kernel is compiled for / chunk size: 4 waves (128 registers, 8 B/lane of scratch) run 2.4 % faster
-// than 3; chunks of 32 traced configurations (64 KB of LDS, two workgroups per CU) 2.7 % slower (GPU session 39)
-#ifndef DNM_RDM_WAVES
-#define DNM_RDM_WAVES 4
-#endif
-#ifndef DNM_RDM_MSTAGE
-#define DNM_RDM_MSTAGE 1024
-#endif
+// The same tile, slices and scratch as rdm_tile_kernel<ST, 6>, with the rank-T update on the matrix cores
+// (rdm_tile.h: rdm_mfma_tile); this kernel is the gather of the dense form.
 template <int ST>
 __global__ void __launch_bounds__(RDM_NT, DNM_RDM_WAVES)
 rdm_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo, int64_t chunks_per_split,
                 int ntiles, c128 *__restrict__ partial) {
-  constexpr int TM = 64;
+  constexpr int TM = RDM_TM;
   constexpr int MST = DNM_RDM_MSTAGE;     // amplitudes per operand in a staged chunk
   constexpr int TK = MST / TM;            // traced configurations per chunk (16: four MFMA steps)
   constexpr int EPT = MST / RDM_NT;       // amplitudes per thread and operand in a chunk
@@ -277,10 +246,8 @@ rdm_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo
 
   const int tid = threadIdx.x;
   const int tile = blockIdx.x;
-  int ti = (int)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-  while ((int64_t)(ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-  while ((int64_t)ti * (ti + 1) / 2 > tile) --ti;
-  const int tj = tile - (int)((int64_t)ti * (ti + 1) / 2);
+  int ti, tj;
+  rdm_tile_coords(tile, &ti, &tj);
   const bool diag_tile = ti == tj;
   const int64_t K = (int64_t)1 << geo.k, T = (int64_t)1 << (geo.L - geo.k);
   const int64_t a0 = (int64_t)ti * TM, b0 = (int64_t)tj * TM;
@@ -290,22 +257,13 @@ rdm_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo
   }
   __syncthreads();
 
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wy = wave >> 1, wx = wave & 1;
-  mfma_acc re[2][2], im[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) re[i][j] = im[i][j] = mfma_acc{0.0, 0.0, 0.0, 0.0};
-
   // the slice of traced configurations of this workgroup (rdm_plan counts it in chunks of RDM_STAGE / TM), walked in
   // chunks of TK from its first configuration
   constexpr int64_t PLAN_TK = RDM_STAGE / TM;
   const int64_t tr_begin = (int64_t)blockIdx.y * chunks_per_split * PLAN_TK;
   int64_t tr_end = tr_begin + chunks_per_split * PLAN_TK;
   if (tr_end > T) tr_end = T;
-  const int64_t c_begin = 0, c_end = tr_end > tr_begin ? (tr_end - tr_begin + TK - 1) / TK : 0;
-  const c128 *Bp = diag_tile ? As : Bs;
+  const int64_t c_end = tr_end > tr_begin ? (tr_end - tr_begin + TK - 1) / TK : 0;
 
   // a thread's amplitudes of a chunk share the row (RDM_NT is a multiple of TM): its part of the state and the
   // bounds tests are loop-invariant; the traced parts of a chunk's TK configurations are deposited once per
@@ -320,8 +278,7 @@ rdm_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo
       pts[c & 1][tid] = tr < tr_end ? rdm_deposit((uint64_t)tr, geo.tlen, geo.tpos, geo.nseg_tr) : ~(uint64_t)0;
     }
   };
-  c128 va[EPT], vb[EPT];
-  auto gather = [&](int64_t c) {
+  auto gather = [&](int64_t c, c128 (&va)[EPT], c128 (&vb)[EPT]) {
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
       const uint64_t pt = pts[c & 1][t0 + i * (RDM_NT / TM)];
@@ -332,80 +289,17 @@ rdm_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo
       }
     }
   };
-  deposit_chunk(c_begin);
-  deposit_chunk(c_begin + 1);
-  __syncthreads();
-  if (c_begin < c_end) gather(c_begin);
-  __syncthreads();                              // every wave has read its slots before deposit_chunk(c_begin + 2)
-  for (int64_t c = c_begin; c < c_end; ++c) {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-      As[tid + i * RDM_NT] = va[i];
-      if (!diag_tile) Bs[tid + i * RDM_NT] = vb[i];
-    }
-    deposit_chunk(c + 2);                       // (its slot was last read by gather(c), before this barrier)
-    __syncthreads();
-    if (c + 1 < c_end) gather(c + 1);           // in flight under the MFMAs below
-#pragma unroll
-    for (int kk = 0; kk < TK; kk += 4) {
-      const int slot = (kk + (lane >> 4)) * TM + (lane & 15);
-      c128 a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = As[slot + wy * 32 + i * 16];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = Bp[slot + wx * 32 + j * 16];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, re[i][j], 0, 0, 0);
-          re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, re[i][j], 0, 0, 0);
-          im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].x, im[i][j], 0, 0, 0);
-          im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[i].x, b[j].y, im[i][j], 0, 0, 0);
-        }
-    }
-    __syncthreads();
-  }
-  c128 *out = partial + ((int64_t)blockIdx.y * ntiles + tile) * (TM * TM);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wy * 32 + i * 16 + (lane >> 4) + 4 * r, col = wx * 32 + j * 16 + (lane & 15);
-        out[row * TM + col] = make_double2(re[i][j][r], im[i][j][r]);
-      }
+  rdm_mfma_tile<MST>(As, Bs, diag_tile, c_end, partial + ((int64_t)blockIdx.y * ntiles + tile) * (TM * TM),
+                     deposit_chunk, gather);
 }
 
 // rho = sum over slices of the partial tiles; the upper triangle is the conjugate transpose
 template <int LOGTM>
 __global__ void __launch_bounds__(RDM_NT)
 rdm_finalize_kernel(const c128 *__restrict__ partial, int ntiles, int nsplit, int64_t K, c128 *__restrict__ rho) {
-  constexpr int TM = 1 << LOGTM;
-  const int tile = blockIdx.x;
-  int ti = (int)((sqrt(8.0 * (double)tile + 1.0) - 1.0) * 0.5);
-  while ((int64_t)(ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-  while ((int64_t)ti * (ti + 1) / 2 > tile) --ti;
-  const int tj = tile - (int)((int64_t)ti * (ti + 1) / 2);
-  for (int e = threadIdx.x; e < TM * TM; e += RDM_NT) {
-    const int r = e / TM, cidx = e % TM;
-    const int64_t a = (int64_t)ti * TM + r, b = (int64_t)tj * TM + cidx;
-    if (a >= K || b >= K) continue;
-    // a diagonal tile holds both triangles, accumulated in different orders (MFMA: the imaginary part of (a, b) and
-    // of (b, a) add the same products in different sequence): the lower one is taken and mirrored like every other
-    // tile, so that rho is Hermitian to the last bit, as the reference's element-by-element sum is
-    if (ti == tj && cidx > r) continue;
-    double sr = 0.0, si = 0.0;
-    for (int s = 0; s < nsplit; ++s) {
-      const c128 v = partial[((int64_t)s * ntiles + tile) * (TM * TM) + e];
-      sr += v.x;
-      si += v.y;
-    }
-    if (a == b) si = 0.0;     // |psi|^2 sums: the reference's a * conj(a) has no imaginary part either
-    rho[a * K + b] = make_double2(sr, si);
-    if (a != b) rho[b * K + a] = make_double2(sr, -si);
-  }
+  int ti, tj;
+  rdm_tile_coords(blockIdx.x, &ti, &tj);
+  rdm_finalize_tile<1 << LOGTM>(partial, ntiles, nsplit, blockIdx.x, ti, tj, K, 1.0, rho);
 }
 
 // tree stage of the slice sum: out[s'] = sum of up to `fan` consecutive slices of `in` (whole slices are
@@ -447,23 +341,21 @@ static int rdm_launch(const c128 *x, const SubView &sub, const RdmGeom &geo, int
   else
     hipLaunchKernelGGL((rdm_tile_kernel<ST, LOGTM>), dim3((unsigned)ntiles, (unsigned)nsplit), dim3(RDM_NT), 0, st, x,
                        sub, geo, chunks_per_split, ntiles, partial);
-  // sum the slices by a fan-in-32 tree (ping-pong inside the scratch), then mirror
-  const int64_t nelem = (int64_t)ntiles * TM * TM;
-  c128 *cur = partial, *nxt = partial + (int64_t)nsplit * nelem;
-  while (nsplit > RDM_FAN) {
-    const int nout = (nsplit + RDM_FAN - 1) / RDM_FAN;
-    hipLaunchKernelGGL(rdm_reduce_kernel, dim3((unsigned)((nelem + RDM_NT - 1) / RDM_NT), (unsigned)nout),
-                       dim3(RDM_NT), 0, st, cur, nxt, nelem, nsplit);
-    cur = nxt;
-    nxt = cur + (int64_t)nout * nelem;
-    nsplit = nout;
-  }
-  hipLaunchKernelGGL((rdm_finalize_kernel<LOGTM>), dim3((unsigned)ntiles), dim3(RDM_NT), 0, st, cur, ntiles,
-                     nsplit, (int64_t)1 << geo.k, rho);
+  // sum the slices by the fan-in-32 tree, then mirror
+  void *level = nullptr;
+  DNM_TRY(rdm_sum_slices(partial, (int64_t)ntiles * TM * TM, &nsplit, &level, st));
+  hipLaunchKernelGGL((rdm_finalize_kernel<LOGTM>), dim3((unsigned)ntiles), dim3(RDM_NT), 0, st, (const c128 *)level,
+                     ntiles, nsplit, (int64_t)1 << geo.k, rho);
   DNM_HIP(hipGetLastError());
   return 0;
 }
 
+// slices + the intermediate levels of the fan-in-32 sum (ns/32 + ns/1024 + ... < ns/31 + 2)
+size_t rdm_partial_bytes(int64_t nsplit, int64_t nelem) {
+  return ((size_t)nsplit + (size_t)nsplit / 31 + 2) * (size_t)nelem * sizeof(c128);
+}
+
+// (ping-pong inside the scratch)
 int rdm_sum_slices(void *partial, int64_t nelem, int *nsplit, void **level, hipStream_t st) {
   c128 *cur = (c128 *)partial, *nxt = cur + (int64_t)*nsplit * nelem;
   int ns = *nsplit;
@@ -512,7 +404,7 @@ void rdm_plan(const RdmGeom &geo, int *logtm, int *ntiles, int *nsplit, int64_t 
       *ntiles = 1;
       *nsplit = (int)ns;
       *chunks_per_split = 0;
-      *partial_bytes = ((size_t)ns + (size_t)ns / 31 + 2) * (size_t)(TMs * TMs) * sizeof(c128);
+      *partial_bytes = rdm_partial_bytes(ns, TMs * TMs);
       return;
     }
   }
@@ -529,8 +421,7 @@ void rdm_plan(const RdmGeom &geo, int *logtm, int *ntiles, int *nsplit, int64_t 
   *ntiles = (int)nt;
   *nsplit = (int)ns;
   *chunks_per_split = cps;
-  // slices + the intermediate levels of the fan-in-32 sum (ns/32 + ns/1024 + ... < ns/31 + 2)
-  *partial_bytes = ((size_t)ns + (size_t)ns / 31 + 2) * (size_t)nt * (size_t)(TM * TM) * sizeof(c128);
+  *partial_bytes = rdm_partial_bytes(ns, nt * TM * TM);
 }
 
 int launch_rdm(const void *x, const SubView &sub, const RdmGeom &geo, void *partial, void *rho, hipStream_t st) {

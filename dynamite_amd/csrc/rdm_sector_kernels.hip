@@ -7,9 +7,9 @@
 // of k - n set bits.  Every product state a | t lies inside the subspace: no fetch is masked, none returns zero, and the
 // work is sum_n C(kA, n)^2 C(L - kA, k - n) products instead of 4^kA 2^(L - kA) (rdm_kernels.hip).
 //
-// One kernel serves every block size: 64 x 64 tiles on v_mfma_f64_16x16x4_f64 with the register blocking, LDS staging
-// and software-pipelined gather of rdm_mfma_kernel; rows and columns past a block's dimension are zero-filled, so a
-// block of dimension < 64 is one padded tile.  The grid runs over a host-built table of (block, tile row, tile column)
+// One kernel serves every block size: the 64 x 64 matrix-core tile of the dense form (rdm_tile.h: rdm_mfma_tile, the
+// one piece of code both kernels run) under a gather of its own; rows and columns past a block's dimension are
+// zero-filled, so a block of dimension < 64 is one padded tile.  The grid runs over a host-built table of (block, tile row, tile column)
 // records, times the slices of the traced index: small blocks ride along with the large ones in one launch.  Slices go
 // to the scratch in the format of the dense form ([slice][tile][64 x 64]) and are summed by the same fan-in tree
 // (rdm_sum_slices); the finalize kernel takes the lower triangle, mirrors it and makes the diagonal real.
@@ -25,30 +25,13 @@
 // x[rank(c)]; the factor 1/2 of the two 1/sqrt 2 is applied once, exactly, by the finalize kernel.  On the contiguous
 // path the complement reverses the order inside a popcount class: rank(~a) = C(kA, n) - 1 - rank_n(a), the run of x is
 // walked downwards.
-#include "kernels.h"
+#include "rdm_tile.h"
 
 namespace dnm {
 
-typedef double2 c128;
-typedef double mfma_acc __attribute__((ext_vector_type(4)));
-
-constexpr int RS_NT = 256;
-constexpr int RS_TM = 64;
+constexpr int RS_TM = RDM_TM;
 constexpr int RS_MST = 1024;             // amplitudes per operand in a staged chunk
 constexpr int RS_TK = RS_MST / RS_TM;    // traced configurations per chunk (16: four MFMA steps)
-
-#ifndef DNM_RDM_WAVES
-#define DNM_RDM_WAVES 4
-#endif
-
-__device__ __forceinline__ uint64_t rs_deposit(uint64_t v, const int8_t *len, const int8_t *pos, int nseg) {
-  uint64_t out = 0;
-  for (int i = 0; i < nseg; ++i) {
-    out |= (v & (((uint64_t)1 << len[i]) - 1)) << pos[i];
-    v >>= len[i];
-  }
-  return out;
-}
 
 // the idx-th pattern of npos bits with nbits set, in ascending order (Sub<SpinConserve>::i2s on npos positions)
 __device__ __forceinline__ uint64_t rs_unrank(int64_t idx, int nbits, int npos, const SubView &s) {
@@ -80,12 +63,12 @@ __device__ __forceinline__ int64_t rs_rank_high(uint64_t t, int shift, int nlow,
 }
 
 template <bool CONTIG, bool XPAR>
-__global__ void __launch_bounds__(RS_NT, DNM_RDM_WAVES)
+__global__ void __launch_bounds__(RDM_NT, DNM_RDM_WAVES)
 rdm_sector_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmGeom geo,
                        const RdmSectorBlock *__restrict__ blocks, const RdmSectorTile *__restrict__ tiles, int ntiles,
                        double sector, c128 *__restrict__ partial) {
   constexpr int TM = RS_TM, MST = RS_MST, TK = RS_TK;
-  constexpr int EPT = MST / RS_NT;        // amplitudes per thread and operand in a chunk
+  constexpr int EPT = MST / RDM_NT;       // amplitudes per thread and operand in a chunk
   __shared__ c128 As[MST];
   __shared__ c128 Bs[MST];
   __shared__ uint64_t pa[TM], pb[TM];
@@ -105,26 +88,17 @@ rdm_sector_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmG
   const uint64_t all = geo.L >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << geo.L) - 1);
   if (!CONTIG) {
     if (tid < TM) {
-      pa[tid] = a0 + tid < D ? rs_deposit(rs_unrank(a0 + tid, blk.n, kA, sub), geo.klen, geo.kpos, geo.nseg_keep) : 0;
-      pb[tid] = b0 + tid < D ? rs_deposit(rs_unrank(b0 + tid, blk.n, kA, sub), geo.klen, geo.kpos, geo.nseg_keep) : 0;
+      pa[tid] = a0 + tid < D ? rdm_deposit(rs_unrank(a0 + tid, blk.n, kA, sub), geo.klen, geo.kpos, geo.nseg_keep) : 0;
+      pb[tid] = b0 + tid < D ? rdm_deposit(rs_unrank(b0 + tid, blk.n, kA, sub), geo.klen, geo.kpos, geo.nseg_keep) : 0;
     }
     __syncthreads();
   }
-
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wy = wave >> 1, wx = wave & 1;
-  mfma_acc re[2][2], im[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) re[i][j] = im[i][j] = mfma_acc{0.0, 0.0, 0.0, 0.0};
 
   // the slice of this block's traced configurations (a multiple of TK per slice; slices past the end are empty)
   const int64_t tr_begin = (int64_t)blockIdx.y * blk.per_slice;
   int64_t tr_end = tr_begin + blk.per_slice;
   if (tr_end > T) tr_end = T;
   const int64_t c_end = tr_end > tr_begin ? (tr_end - tr_begin + TK - 1) / TK : 0;
-  const c128 *Bp = diag_tile ? As : Bs;
 
   const int rr = tid % TM, t0 = tid / TM;
   const uint64_t par = CONTIG ? 0 : pa[rr], pbr = CONTIG ? 0 : pb[rr];
@@ -146,7 +120,7 @@ rdm_sector_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmG
             p = rs_rank_high(t, kA, blk.n, sub);
           }
         } else {
-          p = (int64_t)rs_deposit(t, geo.tlen, geo.tpos, geo.nseg_tr);
+          p = (int64_t)rdm_deposit(t, geo.tlen, geo.tpos, geo.nseg_tr);
         }
       }
       pts[c & 1][tid] = p;
@@ -162,11 +136,10 @@ rdm_sector_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmG
     const c128 v = x[Sub<DNM_SPIN_CONSERVE>::rank((int64_t)s, sub)];
     return make_double2(v.x * cf, v.y * cf);
   };
-  c128 va[EPT], vb[EPT];
-  auto gather = [&](int64_t c) {
+  auto gather = [&](int64_t c, c128 (&va)[EPT], c128 (&vb)[EPT]) {
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
-      const int slot = t0 + i * (RS_NT / TM);
+      const int slot = t0 + i * (RDM_NT / TM);
       const int64_t p = pts[c & 1][slot];
       const int d = pdir[c & 1][slot];
       va[i] = vb[i] = make_double2(0.0, 0.0);
@@ -188,81 +161,17 @@ rdm_sector_mfma_kernel(const c128 *__restrict__ x, const SubView sub, const RdmG
       }
     }
   };
-  deposit_chunk(0);
-  deposit_chunk(1);
-  __syncthreads();
-  if (0 < c_end) gather(0);
-  __syncthreads();                              // every wave has read its slots before deposit_chunk(2)
-  for (int64_t c = 0; c < c_end; ++c) {
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-      As[tid + i * RS_NT] = va[i];
-      if (!diag_tile) Bs[tid + i * RS_NT] = vb[i];
-    }
-    deposit_chunk(c + 2);                       // (its slot was last read by gather(c), before this barrier)
-    __syncthreads();
-    if (c + 1 < c_end) gather(c + 1);           // in flight under the MFMAs below
-#pragma unroll
-    for (int kk = 0; kk < TK; kk += 4) {
-      const int slot = (kk + (lane >> 4)) * TM + (lane & 15);
-      c128 a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = As[slot + wy * 32 + i * 16];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = Bp[slot + wx * 32 + j * 16];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, re[i][j], 0, 0, 0);
-          re[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, re[i][j], 0, 0, 0);
-          im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].x, im[i][j], 0, 0, 0);
-          im[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[i].x, b[j].y, im[i][j], 0, 0, 0);
-        }
-    }
-    __syncthreads();
-  }
-  // C/D layout of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg
-  c128 *out = partial + ((int64_t)blockIdx.y * ntiles + tile) * (TM * TM);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = wy * 32 + i * 16 + (lane >> 4) + 4 * r, col = wx * 32 + j * 16 + (lane & 15);
-        out[row * TM + col] = make_double2(re[i][j][r], im[i][j][r]);
-      }
+  rdm_mfma_tile<MST>(As, Bs, diag_tile, c_end, partial + ((int64_t)blockIdx.y * ntiles + tile) * (TM * TM),
+                     deposit_chunk, gather);
 }
 
-// rho_n = scale * sum over the slices rdm_sum_slices left; the lower triangle is taken and mirrored (a diagonal
-// tile holds both, summed in different orders), the diagonal is made real: Hermitian to the last bit
-__global__ void __launch_bounds__(RS_NT)
+// rho_n = scale * sum over the slices rdm_sum_slices left, mirrored: a tile of the block the table names
+__global__ void __launch_bounds__(RDM_NT)
 rdm_sector_finalize_kernel(const c128 *__restrict__ partial, const RdmSectorBlock *__restrict__ blocks,
                            const RdmSectorTile *__restrict__ tiles, int ntiles, int nsplit, double scale) {
-  constexpr int TM = RS_TM;
-  const int tile = blockIdx.x;
-  const RdmSectorTile rec = tiles[tile];
+  const RdmSectorTile rec = tiles[blockIdx.x];
   const RdmSectorBlock blk = blocks[rec.blk];
-  const int64_t D = blk.dim;
-  c128 *__restrict__ rho = (c128 *)blk.out;
-  for (int e = threadIdx.x; e < TM * TM; e += RS_NT) {
-    const int r = e / TM, cidx = e % TM;
-    const int64_t a = (int64_t)rec.ti * TM + r, b = (int64_t)rec.tj * TM + cidx;
-    if (a >= D || b >= D) continue;
-    if (rec.ti == rec.tj && cidx > r) continue;
-    double sr = 0.0, si = 0.0;
-    for (int s = 0; s < nsplit; ++s) {
-      const c128 v = partial[((int64_t)s * ntiles + tile) * (TM * TM) + e];
-      sr += v.x;
-      si += v.y;
-    }
-    sr *= scale;
-    si *= scale;
-    if (a == b) si = 0.0;
-    rho[a * D + b] = make_double2(sr, si);
-    if (a != b) rho[b * D + a] = make_double2(sr, -si);
-  }
+  rdm_finalize_tile<RS_TM>(partial, ntiles, nsplit, blockIdx.x, rec.ti, rec.tj, blk.dim, scale, (c128 *)blk.out);
 }
 
 int rdm_sector_plan(int nblocks, RdmSectorBlock *blocks, int64_t *ntiles, int *nsplit, size_t *table_bytes,
@@ -293,7 +202,7 @@ int rdm_sector_plan(int nblocks, RdmSectorBlock *blocks, int64_t *ntiles, int *n
   // the two tables at the head of the scratch, then slices + the intermediate levels of the fan-in sum
   size_t tb = (size_t)nblocks * sizeof(RdmSectorBlock) + (size_t)nt * sizeof(RdmSectorTile);
   *table_bytes = (tb + 255) / 256 * 256;
-  *partial_bytes = ((size_t)ns + (size_t)ns / 31 + 2) * (size_t)nt * (size_t)(RS_TM * RS_TM) * sizeof(c128);
+  *partial_bytes = rdm_partial_bytes(ns, nt * (RS_TM * RS_TM));
   return 0;
 }
 
@@ -318,7 +227,7 @@ int launch_rdm_sector(const void *x, const SubView &sub, const RdmGeom &geo, boo
   DNM_HIP(hipMemcpyAsync(dblocks, blocks, (size_t)nblocks * sizeof(RdmSectorBlock), hipMemcpyHostToDevice, st));
   DNM_HIP(hipMemcpyAsync(dtiles, tiles.data(), tiles.size() * sizeof(RdmSectorTile), hipMemcpyHostToDevice, st));
   DNM_HIP(hipStreamSynchronize(st));          // `tiles` is released on return
-  const dim3 grid((unsigned)ntiles, (unsigned)nsplit), wg(RS_NT);
+  const dim3 grid((unsigned)ntiles, (unsigned)nsplit), wg(RDM_NT);
   const c128 *xp = (const c128 *)x;
   const double sector = (double)xparity_sector;
   const int nt = (int)ntiles;
