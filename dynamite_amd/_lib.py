@@ -82,6 +82,16 @@ class DevTab(C.Structure):
                 ("ksign", C.c_uint32), ("nbits", C.c_uint32)]
 
 
+class DevFlip(C.Structure):
+    """plan.h: DevFlip"""
+    _fields_ = [("mask_tile", C.c_uint32), ("mask_pos", C.c_uint32), ("p0", C.c_uint32), ("p1", C.c_uint32),
+                ("pad", C.c_uint32 * 2), ("c", C.c_double)]
+
+
+FL_COUNT = 4
+FL_NAMES = ["tile_thread", "tile_k", "gather_uniform", "gather_boundary"]
+
+
 class Xfer(C.Structure):
     _fields_ = [("partner", C.c_int32), ("pass_id", C.c_int32), ("offset", C.c_int64), ("count", C.c_int64)]
 
@@ -153,6 +163,10 @@ SIGNATURES = {
     "dnm_mat_export_tabs": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_int), f64p, C.c_int64, i64p]),
     "dnm_mat_export_pass": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_int,
                                       C.POINTER(C.c_int)]),
+    "dnm_mat_export_flip": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_uint32), f64p]),
+    "dnm_mat_export_flip_pass": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_int,
+                                           C.POINTER(C.c_int), f64p, C.c_int64, i64p]),
     "dnm_mat_ownership": (C.c_int, [vp, i64p, i64p]),
     "dnm_mat_column_window": (C.c_int, [vp, i64p, i64p, vp]),
     "dnm_mat_column_chunks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), C.c_int64, vp]),

@@ -275,6 +275,259 @@ static bool table_form(const OpForm &op, const RowMask &m, std::vector<uint64_t>
   return nq >= 2 && zs->size() * 45 < nq * 76;
 }
 
+// the operator's diagonal (its mask-0 entry of real terms), or null
+static const RowMask *diagonal_mask(const OpForm &op) {
+  const RowMask *dm = nullptr;
+  for (const RowMask &m : op.masks) if (m.mask == 0 && !m.zero_mask_offdiag) dm = &m;
+  return dm;
+}
+
+// A mask as a flip-flop record (plan.h: DevFlip)?  It flips exactly two bits, its terms are real and see no other bit,
+// and their sum is c on the rows whose two bits differ and nothing on the others: a bond a (XX + YY), c = 2a.  (A Parity
+// mask whose folded bit spreads a sign mask over the index does not qualify, nor does XX alone or a DM term.)
+static FlipBond flip_classify(const RowMask &m) {
+  FlipBond fb;
+  if (__builtin_popcountll(m.mask) != 2 || m.zero_mask_offdiag || m.pack_flip) return fb;
+  fb.b0 = __builtin_ctzll(m.mask);
+  fb.b1 = 63 - __builtin_clzll(m.mask);
+  double f[4] = {0.0, 0.0, 0.0, 0.0};      // the coefficient by (bit b0, bit b1) of the row
+  for (const RowTerm &t : m.terms) {
+    if (t.is_imag || (t.sign & ~m.mask)) return fb;
+    for (int v = 0; v < 4; ++v) {
+      const int par = ((v & 1) && ((t.sign >> fb.b0) & 1)) ^ ((v & 2) && ((t.sign >> fb.b1) & 1));
+      f[v] += par ? -t.coeff : t.coeff;
+    }
+  }
+  if (f[0] != 0.0 || f[3] != 0.0 || f[1] != f[2] || f[1] == 0.0) return fb;
+  fb.c = f[1];
+  fb.ok = true;
+  return fb;
+}
+
+// The tables of the table records of a pass (plan.h: DevTab)
+struct PassTabs {
+  std::vector<DevTab> tile, gather;
+  std::vector<double> vals;
+};
+
+// The records of a pass from a list of diagonal terms (null: none) and the masks that `skip` does not name (empty: all):
+// once for the generic description of the pass (the operator's own diagonal, every mask), once more for the kernel when
+// some of the operator's masks run as flip-flop records (plan.h: DevFlip; build_flip_pass below).  Fills the record
+// ranges of d; the geometry and everything else in d is the caller's.
+static int emit_records(const dnm_mat &A, const PassSpec &ps, int logR, DevPass &d, std::vector<DevQuad> &quads,
+                        std::vector<double> &h_dtile, PassTabs &T, const std::vector<RowTerm> *dterms,
+                        const std::vector<char> &skip) {
+  const OpForm &op = A.op;
+  const int B = ps.B, lognt = B - logR, R = 1 << logR;
+  const int n_eff = ps.n_eff ? ps.n_eff : A.plan.n_loc;
+  const uint64_t tb = ps.tile_bits();
+  std::vector<DevTab> &tabs_tile = T.tile, &tabs_gather = T.gather;
+  std::vector<double> &tabvals = T.vals;
+  auto empty_quad = [&]() {
+    DevQuad q;
+    memset(&q, 0, sizeof(q));
+    return q;
+  };
+  auto set_slot = [&](DevQuad &q, int slot, const RowTerm &t) {
+    q.sign_ext[slot] = t.sign & ~tb;
+    q.sign_tile[slot] = compress_to_tile(t.sign & tb, ps);
+    q.coeff[slot] = t.coeff;
+  };
+  // pack a list of (real) diagonal terms four to a record
+  auto push_diag_list = [&](const std::vector<RowTerm> &lst) {
+    for (size_t i = 0; i < lst.size(); i += 4) {
+      DevQuad q = empty_quad();
+      for (size_t j = i; j < lst.size() && j < i + 4; ++j) {
+        set_slot(q, (int)(j - i), lst[j]);
+        q.nslots = (uint32_t)(j - i + 1);
+      }
+      quads.push_back(q);
+    }
+  };
+
+  if (ps.has_diag) {
+    if (dterms) {
+      d.has_diag = 1;
+      std::vector<RowTerm> lst;
+      for (const RowTerm &t : *dterms)
+        if (compress_to_tile(t.sign & tb, ps) == 0) lst.push_back(t);
+      d.dext_begin = (uint32_t)quads.size();
+      push_diag_list(lst);
+      d.dext_end = (uint32_t)quads.size();
+      // terms inside the tile only: tabulated per tile coordinate (DNM_DIAG_TABLE=0: bucket lists as before)
+      const char *dte = knob("DNM_DIAG_TABLE");
+      const bool use_table = !(dte && dte[0] == '0') && B <= 13;
+      if (use_table) h_dtile.assign((size_t)1 << B, 0.0);
+      // terms that see the tile AND bits outside it, grouped by their sign mask inside the tile (DevPass::gbucket): groups of
+      // three terms or more are summed over the outside bits once per workgroup (DNM_DIAG_GROUPS=0: every term per thread)
+      std::vector<std::pair<uint32_t, std::vector<RowTerm>>> groups;
+      {
+        const char *dge = knob("DNM_DIAG_GROUPS");
+        const bool grouping = !(dge && dge[0] == '0') && !op.packed && !(A.flags & DNM_MAT_USE_GLDS);
+        std::vector<std::pair<uint32_t, std::vector<RowTerm>>> all;
+        if (grouping)
+          for (const RowTerm &t : *dterms) {
+            const uint32_t st = compress_to_tile(t.sign & tb, ps);
+            if (st == 0 || (t.sign & ~tb) == 0) continue;
+            auto it = std::find_if(all.begin(), all.end(), [&](const auto &g) { return g.first == st; });
+            if (it == all.end()) { all.push_back({st, {}}); it = all.end() - 1; }
+            it->second.push_back(t);
+          }
+        std::stable_sort(all.begin(), all.end(), [](const auto &a, const auto &b) { return a.second.size() > b.second.size(); });
+        for (auto &g : all)
+          if (g.second.size() >= 3 && groups.size() < MAXDGROUPS) groups.push_back(std::move(g));
+      }
+      auto grouped = [&](uint32_t st) {
+        return std::any_of(groups.begin(), groups.end(), [&](const auto &g) { return g.first == st; });
+      };
+      for (int j = 0; j < R; ++j) {
+        lst.clear();
+        for (const RowTerm &t : *dterms) {
+          uint32_t st = compress_to_tile(t.sign & tb, ps);
+          if (st == 0 || (int)(st >> lognt) != j) continue;
+          if (use_table && (t.sign & ~tb) == 0) {
+            for (uint32_t tc = 0; tc < (1u << B); ++tc)
+              h_dtile[tc] += (__builtin_popcount(tc & st) & 1) ? -t.coeff : t.coeff;
+          } else if ((t.sign & ~tb) != 0 && grouped(st)) {
+            continue;
+          } else {
+            lst.push_back(t);
+          }
+        }
+        d.dbucket[j] = (uint32_t)quads.size();
+        push_diag_list(lst);
+      }
+      for (int j = R; j <= MAXR; ++j) d.dbucket[j] = (uint32_t)quads.size();
+      // the groups: their term records (the outside part of every sign mask), then one record per group, by k bucket
+      std::vector<std::pair<uint32_t, uint32_t>> where(groups.size());
+      for (size_t g = 0; g < groups.size(); ++g) {
+        std::vector<RowTerm> outside = groups[g].second;
+        for (RowTerm &t : outside) t.sign &= ~tb;
+        where[g].first = (uint32_t)quads.size();
+        push_diag_list(outside);
+        where[g].second = (uint32_t)quads.size() - where[g].first;
+      }
+      for (int j = 0; j < R; ++j) {
+        d.gbucket[j] = (uint32_t)quads.size();
+        for (size_t g = 0; g < groups.size(); ++g) {
+          if ((int)(groups[g].first >> lognt) != j) continue;
+          DevQuad q = empty_quad();
+          q.sign_tile[0] = groups[g].first;
+          q.mask_loc = where[g].first;
+          q.src = where[g].second;
+          q.nslots = 1;
+          quads.push_back(q);
+        }
+      }
+      for (int j = R; j <= MAXR; ++j) d.gbucket[j] = (uint32_t)quads.size();
+    }
+  }
+
+  // off-diagonal masks: records of <= 2 real + <= 2 imaginary terms, sorted into
+  // the kernel's loops (tile/gather x k-variant x real/complex)
+  struct Rec { int loop; DevQuad q; };
+  std::vector<Rec> recs;
+  // masks of many terms as table records (table_form above)
+  auto push_tabs = [&](const RowMask &m, uint64_t mloc, bool gather, int src) -> bool {
+    std::vector<uint64_t> zs;
+    if (!table_form(op, m, &zs)) return false;
+    const int nb = __builtin_popcountll(m.mask);
+    int pb[MAXTABBITS];
+    for (int q = 0, pos = 0; pos < 64; ++pos)
+      if ((m.mask >> pos) & 1ull) pb[q++] = pos;
+    for (uint64_t z : zs) {
+      DevTab T;
+      memset(&T, 0, sizeof(T));
+      T.mask_tile = compress_to_tile(mloc & tb, ps);
+      T.mask_loc = (uint32_t)mloc;
+      T.src = (uint32_t)src;
+      T.nbits = (uint32_t)nb;
+      const uint32_t zt = compress_to_tile(z & tb, ps);
+      T.z_tile = zt & ((1u << lognt) - 1u);
+      T.z_ext = z & ~tb;
+      T.first = (uint32_t)(tabvals.size() / 2);
+      for (int k = 0; k < R; ++k)
+        if (__builtin_popcount((uint32_t)k & (zt >> lognt)) & 1) T.ksign |= 1u << k;
+      for (int q = 0; q < nb; ++q) {
+        if ((tb >> pb[q]) & 1ull) {
+          const int tpos = __builtin_ctz(compress_to_tile((uint64_t)1 << pb[q], ps));
+          if (tpos < lognt) {
+            T.tpos |= (uint32_t)tpos << (8 * q);
+            T.twid |= 1u << (8 * q);
+          } else {
+            T.flags |= 1u;
+            for (int k = 0; k < R; ++k)
+              if ((k >> (tpos - lognt)) & 1) T.ik |= (uint64_t)1 << (4 * k + q);
+          }
+        } else {
+          T.epos |= (uint32_t)pb[q] << (8 * q);
+          T.ewid |= 1u << (8 * q);
+        }
+      }
+      for (int j = 0; j < (1 << nb); ++j) {
+        uint64_t rowbits = 0;
+        for (int q = 0; q < nb; ++q)
+          if ((j >> q) & 1) rowbits |= (uint64_t)1 << pb[q];
+        double re = 0.0, im = 0.0;
+        for (const RowTerm &t : m.terms) {
+          if ((t.sign & ~m.mask) != z) continue;
+          const double c = (__builtin_popcountll(rowbits & t.sign & m.mask) & 1) ? -t.coeff : t.coeff;
+          (t.is_imag ? im : re) += c;
+        }
+        tabvals.push_back(re);
+        tabvals.push_back(im);
+      }
+      if (z == zs.back()) T.flags |= 2u;        // (the groups of a mask: consecutive records, one fetch of the partners)
+      (gather ? tabs_gather : tabs_tile).push_back(T);
+    }
+    return true;
+  };
+  auto push_mask = [&](int idx, bool gather, int src) {
+    const RowMask &m = op.masks[idx];
+    const uint64_t mloc = m.mask & (((uint64_t)1 << n_eff) - 1);
+    if (!gather) DNM_CHECK((mloc & ~tb) == 0, "internal: tile mask leaves the tile");
+    if (push_tabs(m, mloc, gather, src)) return 0;
+    std::vector<const RowTerm *> re, im;
+    for (const RowTerm &t : m.terms) (t.is_imag ? im : re).push_back(&t);
+    size_t ir = 0, ii = 0;
+    while (ir < re.size() || ii < im.size()) {
+      DevQuad q = empty_quad();
+      q.mask_tile = compress_to_tile(mloc & tb, ps);
+      q.mask_loc = (uint32_t)mloc;
+      q.src = (uint32_t)src;
+      q.nslots = m.pack_flip ? 1u : 0u;       // real-packed operators: a lane reads the partner's other lane
+      bool kvar = false, cplx = false;
+      for (int s = 0; s < 2 && ir < re.size(); ++s, ++ir) {
+        set_slot(q, s, *re[ir]);
+        kvar |= (q.sign_tile[s] >> lognt) != 0;
+      }
+      for (int s = 2; s < 4 && ii < im.size(); ++s, ++ii) {
+        set_slot(q, s, *im[ii]);
+        kvar |= (q.sign_tile[s] >> lognt) != 0;
+        cplx = true;
+      }
+      int loop;
+      if (gather) loop = kvar ? (cplx ? LP_GATHER_KVAR_CPLX : LP_GATHER_KVAR_REAL) : (cplx ? LP_GATHER_CPLX : LP_GATHER_REAL);
+      else if (kvar) loop = cplx ? LP_TILE_KVAR_CPLX : LP_TILE_KVAR_REAL;
+      else if (cplx) loop = LP_TILE_CPLX;
+      else loop = (q.mask_tile >> lognt) == 0 ? LP_TILE_REAL_K0 : LP_TILE_REAL;
+      recs.push_back({loop, q});
+    }
+    return 0;
+  };
+  for (int idx : ps.tile_masks)
+    if (skip.empty() || !skip[idx]) DNM_TRY(push_mask(idx, false, 0));
+  for (size_t i = 0; i < ps.gather_masks.size(); ++i)
+    if (skip.empty() || !skip[ps.gather_masks[i]]) DNM_TRY(push_mask(ps.gather_masks[i], true, ps.gather_src[i]));
+  for (int lp = 0; lp < LP_COUNT; ++lp) {
+    d.loop[lp] = (uint32_t)quads.size();
+    for (const Rec &r : recs) if (r.loop == lp) quads.push_back(r.q);
+  }
+  d.loop[LP_COUNT] = (uint32_t)quads.size();
+  d.nquads = (int32_t)quads.size();
+  return 0;
+}
+
 static int build_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
   const OpForm &op = A.op;
   const Plan &pl = A.plan;
@@ -386,220 +639,17 @@ static int build_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
     d.pos_tmask = (uint32_t)tm;
   }
 
+  PassTabs T;
   std::vector<DevQuad> quads;
-  auto empty_quad = [&]() {
-    DevQuad q;
-    memset(&q, 0, sizeof(q));
-    return q;
-  };
-  auto set_slot = [&](DevQuad &q, int slot, const RowTerm &t) {
-    q.sign_ext[slot] = t.sign & ~tb;
-    q.sign_tile[slot] = compress_to_tile(t.sign & tb, ps);
-    q.coeff[slot] = t.coeff;
-  };
-  // pack a list of (real) diagonal terms four to a record
-  auto push_diag_list = [&](const std::vector<RowTerm> &lst) {
-    for (size_t i = 0; i < lst.size(); i += 4) {
-      DevQuad q = empty_quad();
-      for (size_t j = i; j < lst.size() && j < i + 4; ++j) {
-        set_slot(q, (int)(j - i), lst[j]);
-        q.nslots = (uint32_t)(j - i + 1);
-      }
-      quads.push_back(q);
-    }
-  };
-
-  if (ps.has_diag) {
-    const RowMask *dm = nullptr;
-    for (const RowMask &m : op.masks) if (m.mask == 0 && !m.zero_mask_offdiag) dm = &m;
-    if (dm) {
-      d.has_diag = 1;
-      std::vector<RowTerm> lst;
-      for (const RowTerm &t : dm->terms)
-        if (compress_to_tile(t.sign & tb, ps) == 0) lst.push_back(t);
-      d.dext_begin = (uint32_t)quads.size();
-      push_diag_list(lst);
-      d.dext_end = (uint32_t)quads.size();
-      // terms inside the tile only: tabulated per tile coordinate (DNM_DIAG_TABLE=0: bucket lists as before)
-      const char *dte = knob("DNM_DIAG_TABLE");
-      const bool use_table = !(dte && dte[0] == '0') && B <= 13;
-      if (use_table) out->h_dtile.assign((size_t)1 << B, 0.0);
-      // terms that see the tile AND bits outside it, grouped by their sign mask inside the tile (DevPass::gbucket): groups of
-      // three terms or more are summed over the outside bits once per workgroup (DNM_DIAG_GROUPS=0: every term per thread)
-      std::vector<std::pair<uint32_t, std::vector<RowTerm>>> groups;
-      {
-        const char *dge = knob("DNM_DIAG_GROUPS");
-        const bool grouping = !(dge && dge[0] == '0') && !op.packed && !(A.flags & DNM_MAT_USE_GLDS);
-        std::vector<std::pair<uint32_t, std::vector<RowTerm>>> all;
-        if (grouping)
-          for (const RowTerm &t : dm->terms) {
-            const uint32_t st = compress_to_tile(t.sign & tb, ps);
-            if (st == 0 || (t.sign & ~tb) == 0) continue;
-            auto it = std::find_if(all.begin(), all.end(), [&](const auto &g) { return g.first == st; });
-            if (it == all.end()) { all.push_back({st, {}}); it = all.end() - 1; }
-            it->second.push_back(t);
-          }
-        std::stable_sort(all.begin(), all.end(), [](const auto &a, const auto &b) { return a.second.size() > b.second.size(); });
-        for (auto &g : all)
-          if (g.second.size() >= 3 && groups.size() < MAXDGROUPS) groups.push_back(std::move(g));
-      }
-      auto grouped = [&](uint32_t st) {
-        return std::any_of(groups.begin(), groups.end(), [&](const auto &g) { return g.first == st; });
-      };
-      for (int j = 0; j < R; ++j) {
-        lst.clear();
-        for (const RowTerm &t : dm->terms) {
-          uint32_t st = compress_to_tile(t.sign & tb, ps);
-          if (st == 0 || (int)(st >> lognt) != j) continue;
-          if (use_table && (t.sign & ~tb) == 0) {
-            for (uint32_t tc = 0; tc < (1u << B); ++tc)
-              out->h_dtile[tc] += (__builtin_popcount(tc & st) & 1) ? -t.coeff : t.coeff;
-          } else if ((t.sign & ~tb) != 0 && grouped(st)) {
-            continue;
-          } else {
-            lst.push_back(t);
-          }
-        }
-        d.dbucket[j] = (uint32_t)quads.size();
-        push_diag_list(lst);
-      }
-      for (int j = R; j <= MAXR; ++j) d.dbucket[j] = (uint32_t)quads.size();
-      // the groups: their term records (the outside part of every sign mask), then one record per group, by k bucket
-      std::vector<std::pair<uint32_t, uint32_t>> where(groups.size());
-      for (size_t g = 0; g < groups.size(); ++g) {
-        std::vector<RowTerm> outside = groups[g].second;
-        for (RowTerm &t : outside) t.sign &= ~tb;
-        where[g].first = (uint32_t)quads.size();
-        push_diag_list(outside);
-        where[g].second = (uint32_t)quads.size() - where[g].first;
-      }
-      for (int j = 0; j < R; ++j) {
-        d.gbucket[j] = (uint32_t)quads.size();
-        for (size_t g = 0; g < groups.size(); ++g) {
-          if ((int)(groups[g].first >> lognt) != j) continue;
-          DevQuad q = empty_quad();
-          q.sign_tile[0] = groups[g].first;
-          q.mask_loc = where[g].first;
-          q.src = where[g].second;
-          q.nslots = 1;
-          quads.push_back(q);
-        }
-      }
-      for (int j = R; j <= MAXR; ++j) d.gbucket[j] = (uint32_t)quads.size();
-    }
-  }
-
-  // off-diagonal masks: records of <= 2 real + <= 2 imaginary terms, sorted into
-  // the kernel's loops (tile/gather x k-variant x real/complex)
-  struct Rec { int loop; DevQuad q; };
-  std::vector<Rec> recs;
-  // masks of many terms as table records (table_form above)
-  std::vector<DevTab> tabs_tile, tabs_gather;
-  std::vector<double> tabvals;
-  auto push_tabs = [&](const RowMask &m, uint64_t mloc, bool gather, int src) -> bool {
-    std::vector<uint64_t> zs;
-    if (!table_form(op, m, &zs)) return false;
-    const int nb = __builtin_popcountll(m.mask);
-    int pb[MAXTABBITS];
-    for (int q = 0, pos = 0; pos < 64; ++pos)
-      if ((m.mask >> pos) & 1ull) pb[q++] = pos;
-    for (uint64_t z : zs) {
-      DevTab T;
-      memset(&T, 0, sizeof(T));
-      T.mask_tile = compress_to_tile(mloc & tb, ps);
-      T.mask_loc = (uint32_t)mloc;
-      T.src = (uint32_t)src;
-      T.nbits = (uint32_t)nb;
-      const uint32_t zt = compress_to_tile(z & tb, ps);
-      T.z_tile = zt & ((1u << lognt) - 1u);
-      T.z_ext = z & ~tb;
-      T.first = (uint32_t)(tabvals.size() / 2);
-      for (int k = 0; k < R; ++k)
-        if (__builtin_popcount((uint32_t)k & (zt >> lognt)) & 1) T.ksign |= 1u << k;
-      for (int q = 0; q < nb; ++q) {
-        if ((tb >> pb[q]) & 1ull) {
-          const int tpos = __builtin_ctz(compress_to_tile((uint64_t)1 << pb[q], ps));
-          if (tpos < lognt) {
-            T.tpos |= (uint32_t)tpos << (8 * q);
-            T.twid |= 1u << (8 * q);
-          } else {
-            T.flags |= 1u;
-            for (int k = 0; k < R; ++k)
-              if ((k >> (tpos - lognt)) & 1) T.ik |= (uint64_t)1 << (4 * k + q);
-          }
-        } else {
-          T.epos |= (uint32_t)pb[q] << (8 * q);
-          T.ewid |= 1u << (8 * q);
-        }
-      }
-      for (int j = 0; j < (1 << nb); ++j) {
-        uint64_t rowbits = 0;
-        for (int q = 0; q < nb; ++q)
-          if ((j >> q) & 1) rowbits |= (uint64_t)1 << pb[q];
-        double re = 0.0, im = 0.0;
-        for (const RowTerm &t : m.terms) {
-          if ((t.sign & ~m.mask) != z) continue;
-          const double c = (__builtin_popcountll(rowbits & t.sign & m.mask) & 1) ? -t.coeff : t.coeff;
-          (t.is_imag ? im : re) += c;
-        }
-        tabvals.push_back(re);
-        tabvals.push_back(im);
-      }
-      if (z == zs.back()) T.flags |= 2u;        // (the groups of a mask: consecutive records, one fetch of the partners)
-      (gather ? tabs_gather : tabs_tile).push_back(T);
-    }
-    return true;
-  };
-  auto push_mask = [&](int idx, bool gather, int src) {
-    const RowMask &m = op.masks[idx];
-    const uint64_t mloc = m.mask & (((uint64_t)1 << n_eff) - 1);
-    if (!gather) DNM_CHECK((mloc & ~tb) == 0, "internal: tile mask leaves the tile");
-    if (push_tabs(m, mloc, gather, src)) return 0;
-    std::vector<const RowTerm *> re, im;
-    for (const RowTerm &t : m.terms) (t.is_imag ? im : re).push_back(&t);
-    size_t ir = 0, ii = 0;
-    while (ir < re.size() || ii < im.size()) {
-      DevQuad q = empty_quad();
-      q.mask_tile = compress_to_tile(mloc & tb, ps);
-      q.mask_loc = (uint32_t)mloc;
-      q.src = (uint32_t)src;
-      q.nslots = m.pack_flip ? 1u : 0u;       // real-packed operators: a lane reads the partner's other lane
-      bool kvar = false, cplx = false;
-      for (int s = 0; s < 2 && ir < re.size(); ++s, ++ir) {
-        set_slot(q, s, *re[ir]);
-        kvar |= (q.sign_tile[s] >> lognt) != 0;
-      }
-      for (int s = 2; s < 4 && ii < im.size(); ++s, ++ii) {
-        set_slot(q, s, *im[ii]);
-        kvar |= (q.sign_tile[s] >> lognt) != 0;
-        cplx = true;
-      }
-      int loop;
-      if (gather) loop = kvar ? (cplx ? LP_GATHER_KVAR_CPLX : LP_GATHER_KVAR_REAL) : (cplx ? LP_GATHER_CPLX : LP_GATHER_REAL);
-      else if (kvar) loop = cplx ? LP_TILE_KVAR_CPLX : LP_TILE_KVAR_REAL;
-      else if (cplx) loop = LP_TILE_CPLX;
-      else loop = (q.mask_tile >> lognt) == 0 ? LP_TILE_REAL_K0 : LP_TILE_REAL;
-      recs.push_back({loop, q});
-    }
-    return 0;
-  };
-  for (int idx : ps.tile_masks) DNM_TRY(push_mask(idx, false, 0));
-  for (size_t i = 0; i < ps.gather_masks.size(); ++i)
-    DNM_TRY(push_mask(ps.gather_masks[i], true, ps.gather_src[i]));
-  for (int lp = 0; lp < LP_COUNT; ++lp) {
-    d.loop[lp] = (uint32_t)quads.size();
-    for (const Rec &r : recs) if (r.loop == lp) quads.push_back(r.q);
-  }
-  d.loop[LP_COUNT] = (uint32_t)quads.size();
-
-  d.nquads = (int32_t)quads.size();
+  const RowMask *dm = diagonal_mask(op);
+  DNM_TRY(emit_records(A, ps, logR, d, quads, out->h_dtile, T, dm ? &dm->terms : nullptr, std::vector<char>()));
   d.need_tile = (d.has_diag || !ps.tile_masks.empty()) ? 1 : 0;
   d.tab_loop[0] = 0;
-  d.tab_loop[1] = (uint32_t)tabs_tile.size();
-  d.tab_loop[2] = (uint32_t)(tabs_tile.size() + tabs_gather.size());
-  out->h_tabs = tabs_tile;
-  out->h_tabs.insert(out->h_tabs.end(), tabs_gather.begin(), tabs_gather.end());
-  out->h_tabvals = tabvals;
+  d.tab_loop[1] = (uint32_t)T.tile.size();
+  d.tab_loop[2] = (uint32_t)(T.tile.size() + T.gather.size());
+  out->h_tabs = T.tile;
+  out->h_tabs.insert(out->h_tabs.end(), T.gather.begin(), T.gather.end());
+  out->h_tabvals = T.vals;
   d.tabs = nullptr;
   d.tabvals = nullptr;
   if (!out->h_tabs.empty() && !A.host_only) {
@@ -623,12 +673,167 @@ static int build_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
   return 0;
 }
 
+// The masks of an operator that run as flip-flop records (plan.h: DevFlip), decided ONCE per operator, after its passes
+// have been built generically: A->flip_bonds[i] for op.masks[i].  None (DNM_FLIPFLOP=0, or an operator that needs another
+// kernel instance: real-packed, late gathers, or any local pass whose generic form has table records or grouped diagonal
+// terms -- read off the passes as emit_records built them) leaves the vector empty.
+//   gathered masks: no condition beyond flip_classify (nothing changes but the record);
+//   tile masks run as exchanges, which take a = c / 2 off the ZZ term on the bond's pair: taken only where the diagonal HAS
+//   that term.  The reduced diagonal then has no sign mask that the operator's own lacks, so whatever emit_records groups
+//   of it is a subset of what it grouped before -- a pass without grouped terms stays without.  (An XY bond would ADD a
+//   term per bond, across the tile boundary of the diagonal pass one that every thread evaluates, three of them on one
+//   spin a group: such bonds keep their generic tile records.)
+static void decide_flip_bonds(dnm_mat *A) {
+  const OpForm &op = A->op;
+  const Plan &pl = A->plan;
+  A->flip_bonds.clear();
+  const char *e = knob("DNM_FLIPFLOP");
+  if ((e && e[0] == '0') || op.packed || !(pl.cfg.cache_policy & 32)) return;
+  const RowMask *dm = diagonal_mask(op);
+  bool diag_pass = false;
+  for (size_t i = 0; i < pl.local.size(); ++i) {
+    const DevPass &d = A->local_passes[i]->desc;
+    if (d.tab_loop[2] > 0 || d.gbucket[MAXR] > d.gbucket[0]) return;
+    diag_pass = diag_pass || d.has_diag;
+  }
+  std::vector<FlipBond> bonds(op.masks.size());
+  bool any = false;
+  for (const PassSpec &ps : pl.local) {
+    for (int idx : ps.tile_masks) {
+      FlipBond fb = flip_classify(op.masks[idx]);
+      const uint64_t pair = op.masks[idx].mask;
+      fb.exch = fb.ok && diag_pass && dm &&
+                std::any_of(dm->terms.begin(), dm->terms.end(), [&](const RowTerm &t) { return t.sign == pair; });
+      fb.ok = fb.exch;
+      bonds[idx] = fb;
+      any = any || fb.ok;
+    }
+    for (size_t i = 0; i < ps.gather_masks.size(); ++i) {
+      if (ps.gather_src[i] != 0) continue;
+      bonds[ps.gather_masks[i]] = flip_classify(op.masks[ps.gather_masks[i]]);
+      any = any || bonds[ps.gather_masks[i]].ok;
+    }
+  }
+  if (any) A->flip_bonds.swap(bonds);
+}
+
+// What the kernel runs on when the operator has flip-flop records: the records of this local pass, the generic records
+// that remain and the diagonal as the exchanges leave it (out->fdesc, built by the same emit_records)
+static int build_flip_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
+  const OpForm &op = A.op;
+  const Plan &pl = A.plan;
+  const std::vector<FlipBond> &bonds = A.flip_bonds;
+  if (bonds.empty()) return 0;
+  const DevPass &d = out->desc;
+  const int lognt = d.tile_bits - d.log_rows;
+  const uint64_t tb = ps.tile_bits();
+  std::vector<char> skip(op.masks.size(), 0);
+  std::vector<DevFlip> fl[FL_COUNT];
+  const int S = pl.cfg.swz;
+  auto add_flip = [&](int idx, bool gather) {
+    const FlipBond &fb = bonds[idx];
+    if (!fb.ok) return;
+    DevFlip f;
+    memset(&f, 0, sizeof(f));
+    f.c = fb.c;
+    const uint64_t b0 = (uint64_t)1 << fb.b0, b1 = (uint64_t)1 << fb.b1;
+    int cls;
+    if (!gather) {
+      f.mask_tile = compress_to_tile(b0 | b1, ps);
+      f.p0 = (uint32_t)__builtin_ctz(f.mask_tile);
+      f.p1 = 31u - (uint32_t)__builtin_clz(f.mask_tile);
+      cls = (int)f.p1 < lognt ? FL_TILE_T : FL_TILE_K;
+    } else {
+      const uint64_t mloc = b0 | b1;
+      f.mask_pos = (uint32_t)(S ? (mloc ^ (((mloc >> S) & (((uint64_t)1 << (S - 4)) - 1)) << 4)) : mloc);
+      if (!(tb & mloc)) {
+        f.p0 = (uint32_t)fb.b0;
+        f.p1 = (uint32_t)fb.b1;
+        cls = FL_GATHER_U;
+      } else {
+        const bool low_in = (tb & b0) != 0;        // (a gather mask has a bit outside the tile)
+        f.p0 = (uint32_t)__builtin_ctz(compress_to_tile(low_in ? b0 : b1, ps));
+        f.p1 = (uint32_t)(low_in ? fb.b1 : fb.b0);
+        cls = FL_GATHER_B;
+      }
+    }
+    fl[cls].push_back(f);
+    skip[idx] = 1;
+  };
+  for (int idx : ps.tile_masks) add_flip(idx, false);
+  for (int idx : ps.gather_masks) add_flip(idx, true);
+  // the diagonal as the exchanges leave it: per bond that runs as an exchange (in whichever local pass) the ZZ term on
+  // its pair loses a = c / 2 (an isotropic bond's is gone), and -a joins the constant
+  const RowMask *dm = diagonal_mask(op);
+  std::vector<RowTerm> dterms;
+  if (dm) dterms = dm->terms;
+  double dconst = 0.0;
+  bool diag_changed = false;
+  if (ps.has_diag)
+    for (size_t idx = 0; idx < bonds.size(); ++idx) {
+      if (!bonds[idx].exch) continue;
+      const double a = 0.5 * bonds[idx].c;
+      const uint64_t pair = op.masks[idx].mask;
+      auto it = std::find_if(dterms.begin(), dterms.end(), [&](const RowTerm &t) { return t.sign == pair; });
+      DNM_CHECK(it != dterms.end(), "internal: an exchange without a ZZ term on its pair");
+      if (it->coeff == a) dterms.erase(it);
+      else it->coeff -= a;
+      dconst -= a;
+      diag_changed = true;
+    }
+  size_t nflip = 0;
+  for (int c = 0; c < FL_COUNT; ++c) nflip += fl[c].size();
+  if (nflip == 0 && !diag_changed) return 0;
+  out->fdesc = d;
+  PassTabs T;
+  DNM_TRY(emit_records(A, ps, d.log_rows, out->fdesc, out->h_fquads, out->h_fdtile, T, dm ? &dterms : nullptr, skip));
+  // (what decide_flip_bonds relies on: the reduced pass needs no other kernel instance than the flip-flop one)
+  DNM_CHECK(T.tile.empty() && T.gather.empty() && out->fdesc.gbucket[MAXR] == out->fdesc.gbucket[0],
+            "internal: the flip-flop form of a pass has table records or grouped diagonal terms");
+  DevFlipPass &fp = out->flip;
+  memset(&fp, 0, sizeof(fp));
+  for (int c = 0; c < FL_COUNT; ++c) {
+    fp.loop[c] = (uint32_t)out->h_flips.size();
+    out->h_flips.insert(out->h_flips.end(), fl[c].begin(), fl[c].end());
+  }
+  fp.loop[FL_COUNT] = (uint32_t)out->h_flips.size();
+  if (out->h_flips.empty()) out->h_flips.push_back(DevFlip{});      // (a pass that only carries the reduced diagonal)
+  fp.dconst = dconst;
+  out->fdesc.quads = nullptr;
+  out->fdesc.dtile = nullptr;
+  if (!A.host_only) {
+    DNM_TRY(out->flips.upload(out->h_flips.data(), out->h_flips.size() * sizeof(DevFlip)));
+    DNM_TRY(out->fquads.upload(out->h_fquads.data(), out->h_fquads.size() * sizeof(DevQuad)));
+    fp.recs = (const DevFlip *)out->flips.p;
+    out->fdesc.quads = (const DevQuad *)out->fquads.p;
+    if (!out->h_fdtile.empty()) {
+      DNM_TRY(out->fdtile.upload(out->h_fdtile.data(), out->h_fdtile.size() * sizeof(double)));
+      out->fdesc.dtile = (const double *)out->fdtile.p;
+    }
+  }
+  return 0;
+}
+
 static hipStream_t S(void *stream) { return (hipStream_t)stream; }
 
 // d: the pass descriptor with this call's fields filled in; p: the pass it was copied from
 static int launch_pass(const dnm_mat *A, const PassOnDevice &p, const DevPass &d, const void *x, void *y,
                        const void *xr, hipStream_t st, unsigned nparts = 1) {
-  return launch_tile_pass(d, d.tile_bits, d.log_rows, (A->flags & DNM_MAT_USE_GLDS) != 0, p.n_eff, x, y, xr, st, nparts);
+  const bool glds = (A->flags & DNM_MAT_USE_GLDS) != 0;
+  if (p.h_flips.empty()) return launch_tile_pass(d, d.tile_bits, d.log_rows, glds, p.n_eff, x, y, xr, st, nparts);
+  // flip-flop records: this call's fields of d on the descriptor the kernel runs on
+  DevPass f = d;
+  const DevPass &k = p.fdesc;
+  f.quads = k.quads;
+  f.dtile = k.dtile;
+  f.nquads = k.nquads;
+  f.has_diag = k.has_diag;
+  f.dext_begin = k.dext_begin;
+  f.dext_end = k.dext_end;
+  memcpy(f.dbucket, k.dbucket, sizeof(f.dbucket));
+  memcpy(f.gbucket, k.gbucket, sizeof(f.gbucket));
+  memcpy(f.loop, k.loop, sizeof(f.loop));
+  return launch_tile_pass(f, f.tile_bits, f.log_rows, glds, p.n_eff, x, y, xr, st, nparts, &p.flip);
 }
 
 // partial sums a pass writes to dot_out: one per tile
@@ -1309,6 +1514,10 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
         DNM_TRY(build_pass(*A, ps, p.get()));
         A->remote_passes.push_back(std::move(p));
       }
+      // flip-flop records (plan.h: DevFlip): decided for the operator as a whole, from its passes as they stand
+      decide_flip_bonds(A.get());
+      for (size_t i = 0; i < A->plan.local.size(); ++i)
+        DNM_TRY(build_flip_pass(*A, A->plan.local[i], A->local_passes[i].get()));
     }
   }
   *out = A.release();
@@ -2038,6 +2247,7 @@ int dnm_mat_plan_describe(const dnm_mat *A, char *buf, size_t buflen) {
     for (const auto &p : A->local_passes) { ntab += p->h_tabs.size(); nquad += p->desc.loop[LP_COUNT] - p->desc.loop[0]; }
     for (const auto &p : A->remote_passes) { ntab += p->h_tabs.size(); nquad += p->desc.loop[LP_COUNT] - p->desc.loop[0]; }
     if (ntab) s += "table records: " + std::to_string(ntab) + " (beside " + std::to_string(nquad) + " records of four terms)\n";
+    // (flip-flop records -- plan.h: DevFlip -- add no line: tests pin the line count of the chain plans; dnm_mat_export_flip)
   }
   snprintf(buf, buflen, "%s", s.c_str());
   return 0;
@@ -2090,6 +2300,53 @@ int dnm_mat_export_dtile(const dnm_mat *A, int remote, int idx, double *out, int
   DNM_CHECK((int64_t)p.h_dtile.size() == n, "the pass has %zu tabulated diagonal entries, not %lld", p.h_dtile.size(),
             (long long)n);
   memcpy(out, p.h_dtile.data(), p.h_dtile.size() * sizeof(double));
+  return 0;
+}
+
+int dnm_mat_export_flip(const dnm_mat *A, int remote, int idx, void *flips_out, size_t flip_bytes, int max_flips,
+                        int *nflips, uint32_t *loops_out, double *dconst) {
+  DNM_CHECK(A && nflips, "null argument");
+  const auto &v = remote ? A->remote_passes : A->local_passes;
+  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
+  const PassOnDevice &p = *v[idx];
+  if (p.h_flips.empty()) {      // the pass runs on its generic records
+    *nflips = -1;
+    return 0;
+  }
+  *nflips = (int)p.flip.loop[FL_COUNT];
+  if (loops_out) memcpy(loops_out, p.flip.loop, sizeof(p.flip.loop));
+  if (dconst) *dconst = p.flip.dconst;
+  if (flips_out && *nflips > 0) {
+    DNM_CHECK(flip_bytes == sizeof(DevFlip), "DevFlip size mismatch (%zu vs %zu)", flip_bytes, sizeof(DevFlip));
+    DNM_CHECK(max_flips >= *nflips, "record buffer too small");
+    memcpy(flips_out, p.h_flips.data(), (size_t)*nflips * sizeof(DevFlip));
+  }
+  return 0;
+}
+
+int dnm_mat_export_flip_pass(const dnm_mat *A, int remote, int idx, void *desc_out, size_t desc_bytes, void *quads_out,
+                             size_t quad_bytes, int max_quads, int *nquads, double *dtile_out, int64_t max_dtile,
+                             int64_t *ndtile) {
+  DNM_CHECK(A && nquads && ndtile, "null argument");
+  const auto &v = remote ? A->remote_passes : A->local_passes;
+  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
+  const PassOnDevice &p = *v[idx];
+  DNM_CHECK(!p.h_flips.empty(), "the pass has no flip-flop form");
+  *nquads = (int)p.h_fquads.size();
+  *ndtile = (int64_t)p.h_fdtile.size();
+  if (desc_out) {
+    DNM_CHECK(desc_bytes == sizeof(DevPass), "DevPass size mismatch (%zu vs %zu)", desc_bytes, sizeof(DevPass));
+    memcpy(desc_out, &p.fdesc, sizeof(DevPass));
+  }
+  if (quads_out && !p.h_fquads.empty()) {
+    DNM_CHECK(quad_bytes == sizeof(DevQuad), "DevQuad size mismatch (%zu vs %zu)", quad_bytes, sizeof(DevQuad));
+    DNM_CHECK(max_quads >= *nquads, "record buffer too small");
+    memcpy(quads_out, p.h_fquads.data(), p.h_fquads.size() * sizeof(DevQuad));
+  }
+  if (dtile_out && !p.h_fdtile.empty()) {
+    DNM_CHECK(max_dtile >= *ndtile, "table buffer too small");
+    memcpy(dtile_out, p.h_fdtile.data(), p.h_fdtile.size() * sizeof(double));
+  }
   return 0;
 }
 

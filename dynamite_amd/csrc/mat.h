@@ -43,9 +43,26 @@ struct PassOnDevice {
   std::vector<DevTab> h_tabs;     // table records (plan.h: DevTab) and their tables, host copies
   std::vector<double> h_tabvals;
   DevBuf tabs, tabvals;
+  // passes with flip-flop records (plan.h: DevFlip): what the kernel runs on -- the flip-flop records, and fdesc with the
+  // remaining generic records (h_fquads) and the reduced diagonal (h_fdtile); desc / h_quads / h_dtile above keep
+  // describing the whole pass generically
+  std::vector<DevFlip> h_flips;
+  DevFlipPass flip{};
+  DevPass fdesc{};
+  std::vector<DevQuad> h_fquads;
+  std::vector<double> h_fdtile;
+  DevBuf flips, fquads, fdtile;
   int partner = -1;
   int n_eff = 0;                  // index bits the pass sweeps
   int64_t y_off = 0, src_off = 0; // partner passes: first local row / first partner amplitude
+};
+
+// A mask as a flip-flop record (plan.h: DevFlip; flip_classify / decide_flip_bonds in mat.cpp)
+struct FlipBond {
+  bool ok = false;        // the mask runs as a flip-flop record
+  bool exch = false;      // ... as a tile record, an exchange: the diagonal carries what it leaves
+  int b0 = 0, b1 = 0;     // the two index bits, b0 < b1
+  double c = 0.0;         // the coefficient on rows whose two bits differ
 };
 
 int rdm_release_scratch();   // frees the cached scratch of dnm_reduced_density_matrix
@@ -78,6 +95,7 @@ struct dnm_mat {
   dnm::OpForm op;
   dnm::Plan plan;
   std::vector<std::unique_ptr<dnm::PassOnDevice>> local_passes, remote_passes;
+  std::vector<dnm::FlipBond> flip_bonds;   // per op.masks entry; empty: the operator has no flip-flop records
 
   // generic-kernel tables
   dnm::DevBuf d_masks, d_offsets, d_signs, d_rcoeffs;

@@ -87,6 +87,11 @@ __device__ __forceinline__ double flip_sign(double c, uint32_t parity_bit) {
 // signed amplitude of slot j of a record for this thread: coeff * (-1)^popcount(row & sign)
 // restricted to the thread-constant part of the row (tile coordinate `tt`, block part `sbase`)
 __device__ __forceinline__ double slot_amp(CQuad &q, int j, uint32_t tt, uint64_t sbase) {
+#ifdef DNM_PROBE_UNSIGNED_SLOTS
+  // timing probe, WRONG RESULTS (tools/build_variant.py ... -- -DDNM_PROBE_UNSIGNED_SLOTS): what the generic records
+  // would cost without their sign evaluation -- the bound on what flip-flop records can save there
+  return q.coeff[j];
+#endif
   uint32_t p = (uint32_t)(__popc(tt & q.sign_tile[j]) + __popcll(sbase & q.sign_ext[j])) & 1u;
   return flip_sign(q.coeff[j], p);
 }
@@ -236,6 +241,106 @@ __device__ __forceinline__ void apply_records(CQuad *__restrict__ quads, uint32_
   }
 }
 
+// Flip-flop records (plan.h: DevFlip).  Tile records, an exchange: y[r] += c x[swap(r)], swap(r) = r ^ mask where the
+// record's two bits differ and r where they agree -- no sign, one scalar coefficient, every multiply-add useful.  The
+// loop is software-pipelined by hand: the LDS reads of record i + 1 are issued before the multiply-adds of record i
+// (two sets of partner registers, which the record's lack of slot amplitudes and sign temporaries pays for).
+//   TBITS: both bits are thread bits -- the rows of a thread share the decision, one address with immediate offsets
+typedef const __attribute__((address_space(4))) DevFlip CFlip;
+
+// what a tile record says, in scalar registers
+struct FlipRec {
+  uint32_t p0, p1, mt;
+  double c;
+};
+__device__ __forceinline__ FlipRec flip_rec(CFlip &F) { return FlipRec{F.p0, F.p1, F.mask_tile, F.c}; }
+
+template <int R, int LOGNT, bool TBITS>
+__device__ __forceinline__ void flip_read(const FlipRec &F, const c128 *tile, uint32_t tid, c128 (&xv)[R]) {
+  constexpr uint32_t NT = 1u << LOGNT;
+  if constexpr (TBITS) {
+    const uint32_t differ = ((tid >> F.p0) ^ (tid >> F.p1)) & 1u;
+    const c128 *p = tile + (tid ^ (F.mt & (0u - differ)));
+#pragma unroll
+    for (int k = 0; k < R; ++k) xv[k] = p[k * NT];
+  } else {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const uint32_t tc = tid | ((uint32_t)k << LOGNT);
+      const uint32_t differ = ((tc >> F.p0) ^ (tc >> F.p1)) & 1u;
+      xv[k] = tile[tc ^ (F.mt & (0u - differ))];
+    }
+  }
+}
+
+template <int R>
+__device__ __forceinline__ void flip_fma(double c, const c128 (&xv)[R], double (&ar)[R], double (&ai)[R]) {
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    ar[k] = fma(c, xv[k].x, ar[k]);
+    ai[k] = fma(c, xv[k].y, ai[k]);
+  }
+}
+
+template <int R, int LOGNT, bool TBITS>
+__device__ __forceinline__ void flip_tile(CFlip *__restrict__ flips, uint32_t b, uint32_t e, double (&ar)[R],
+                                          double (&ai)[R], const c128 *tile, uint32_t tid) {
+  if (b >= e) return;
+  // Two records per trip, each set of partner registers refilled as soon as its multiply-adds are issued.  The records
+  // themselves are read a trip ahead: scalar loads and LDS reads share a counter, and a scalar load between the LDS
+  // reads of one record and their use would make that use wait for everything.  Indices past the end fall back on the
+  // last record (read, never used); an odd count ends on the set the last trip filled.
+  const uint32_t last = e - 1;
+  auto rec = [&](uint32_t i) { return flip_rec(flips[i < last ? i : last]); };
+  c128 xa[R], xb[R];
+  FlipRec f0 = rec(b), f1 = rec(b + 1);
+  flip_read<R, LOGNT, TBITS>(f0, tile, tid, xa);
+  uint32_t qi = b;
+  for (; qi + 1 < e; qi += 2) {
+    const FlipRec g0 = rec(qi + 2), g1 = rec(qi + 3);
+    flip_read<R, LOGNT, TBITS>(f1, tile, tid, xb);
+    flip_fma<R>(f0.c, xa, ar, ai);
+    flip_read<R, LOGNT, TBITS>(g0, tile, tid, xa);
+    flip_fma<R>(f1.c, xb, ar, ai);
+    f0 = g0;
+    f1 = g1;
+  }
+  if (qi < e) flip_fma<R>(f0.c, xa, ar, ai);
+}
+
+// Gathered flip-flop records: the partners are fetched only where the record's bits differ.  [b, m): both bits lie
+// outside the tile -- the whole workgroup fetches or skips, decided from sbase on the scalar unit; [m, e): one bit is a
+// tile bit -- the rows whose bit agrees with the outside one fetch nothing (a thread bit: half the lanes; a k bit: half
+// the rows of every thread).
+template <int R, int LOGNT>
+__device__ __forceinline__ void flip_gathers(CFlip *__restrict__ flips, uint32_t b, uint32_t m, uint32_t e, double (&ar)[R],
+                                             double (&ai)[R], const RowAddr<R> &RA, const c128 *__restrict__ x,
+                                             uint32_t tid, uint64_t sbase) {
+  for (uint32_t qi = b; qi < m; ++qi) {
+    CFlip &F = flips[qi];
+    if (!((uint32_t)((sbase >> F.p0) ^ (sbase >> F.p1)) & 1u)) continue;
+    const uint32_t xm = F.mask_pos;
+    c128 xv[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) xv[k] = *RA.at(x, k, xm);
+    flip_fma<R>(F.c, xv, ar, ai);
+  }
+  for (uint32_t qi = m; qi < e; ++qi) {
+    CFlip &F = flips[qi];
+    const uint32_t xm = F.mask_pos;
+    const uint32_t outer = (uint32_t)(sbase >> F.p1) & 1u;
+    const uint32_t p0 = F.p0;
+    c128 xv[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const uint32_t tc = tid | ((uint32_t)k << LOGNT);
+      xv[k] = make_double2(0.0, 0.0);
+      if ((((tc >> p0) & 1u) ^ outer) != 0u) xv[k] = *RA.at(x, k, xm);
+    }
+    flip_fma<R>(F.c, xv, ar, ai);
+  }
+}
+
 // Table records (plan.h: DevTab): one per mask (or group of a mask's terms) -- the coefficient of a row is a parity times
 // a table entry picked by the row's bits at the flipped positions.  Thread part of the index from tid (bits that lie in
 // the block part or in the k bits are scalar), one 16-byte load of the entry (R of them when a flipped bit is a k bit).
@@ -362,10 +467,11 @@ constexpr int tile_waves_per_simd(int B, int LOGR, bool TAB = false) {
 // requests).  (Two records in flight was tried: spills at 8 rows per thread, no gain at 16.)
 // TAB: the instance that also knows table records (DevPass::tabs; passes without any run on the plain one, which this
 // parameter leaves as it was)
-template <int B, int LOGR, bool GLDS, int GV, bool PACK = false, bool TAB = false>
-__global__ void __launch_bounds__(1 << (B - LOGR), tile_waves_per_simd(B, LOGR, TAB))
-tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__ y,
-                 const c128 *__restrict__ xr) {
+// FLIP: the instance that also knows flip-flop records (plan.h: DevFlip, FP: their ranges and the constant of the
+// diagonal); passes without any run on the instances without, which this parameter leaves as they were
+template <int B, int LOGR, bool GLDS, int GV, bool PACK, bool TAB, bool FLIP>
+__device__ __forceinline__ void tile_pass_body(const DevPass &P, const c128 *__restrict__ x, c128 *__restrict__ y,
+                                               const c128 *__restrict__ xr, const DevFlipPass &FP) {
   constexpr int R = 1 << LOGR;
   constexpr int LOGNT = B - LOGR;
   constexpr uint32_t NT = 1u << LOGNT;
@@ -474,6 +580,9 @@ tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__
     DNM_LOOP(LP_GATHER_KVAR_CPLX, true, true, true, false);
   }
 #undef DNM_LOOP
+  if constexpr (FLIP)
+    flip_gathers<R, LOGNT>((CFlip *)FP.recs, FP.loop[FL_GATHER_U], FP.loop[FL_GATHER_B], FP.loop[FL_GATHER_B + 1], ar, ai, RA,
+                           x, tid, sbase);
   c128 *tabl = nullptr;
   if constexpr (TAB) {
     __shared__ __attribute__((aligned(16))) unsigned char tabl_mem[TABL_ENTRIES * 16];
@@ -540,6 +649,7 @@ tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__
 #pragma unroll
     for (int j = 0; j < R; ++j) D[j] = 0.0;
     D[0] = dext;
+    if constexpr (FLIP) D[0] += FP.dconst;
     double dtab[R];
     if (P.dtile) {      // tile-only terms, tabulated per tile coordinate (L2-resident)
 #pragma unroll
@@ -594,6 +704,10 @@ tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__
   // ---- off-diagonal masks, one branch-free loop per record class
 #define DNM_LOOP(LP, KV, CX, GA, KZ) \
   apply_records<R, LOGNT, KV, CX, GA, KZ, PACK>(quads, P.loop[LP], P.loop[LP + 1], ar, ai, tile, RA, x, xr, tid, sbase, skw, P.swz_xor_src)
+  if constexpr (FLIP) {
+    flip_tile<R, LOGNT, true>((CFlip *)FP.recs, FP.loop[FL_TILE_T], FP.loop[FL_TILE_T + 1], ar, ai, tile, tid);
+    flip_tile<R, LOGNT, false>((CFlip *)FP.recs, FP.loop[FL_TILE_K], FP.loop[FL_TILE_K + 1], ar, ai, tile, tid);
+  }
   DNM_LOOP(LP_TILE_REAL_K0, false, false, false, true);
   DNM_LOOP(LP_TILE_REAL, false, false, false, false);
   DNM_LOOP(LP_TILE_CPLX, false, true, false, false);
@@ -675,6 +789,21 @@ tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__
   }
 }
 
+template <int B, int LOGR, bool GLDS, int GV, bool PACK = false, bool TAB = false>
+__global__ void __launch_bounds__(1 << (B - LOGR), tile_waves_per_simd(B, LOGR, TAB))
+tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__ y,
+                 const c128 *__restrict__ xr) {
+  tile_pass_body<B, LOGR, GLDS, GV, PACK, TAB, false>(P, x, y, xr, DevFlipPass{});
+}
+
+// passes with flip-flop records (early gathers; no table records, no real-packed form)
+template <int B, int LOGR, bool GLDS>
+__global__ void __launch_bounds__(1 << (B - LOGR), tile_waves_per_simd(B, LOGR, false))
+tile_pass_flip_kernel(const DevPass P, const DevFlipPass FP, const c128 *__restrict__ x, c128 *__restrict__ y,
+                      const c128 *__restrict__ xr) {
+  tile_pass_body<B, LOGR, GLDS, 1, false, false, true>(P, x, y, xr, FP);
+}
+
 #ifdef DNM_PHASE_TIMING
 }  // namespace dnm
 extern "C" int dnm_debug_phase_buffer(void *buf) {
@@ -687,7 +816,7 @@ namespace dnm {
 // ---------------------------------------------------------------------------
 template <int B, int LOGR>
 static int launch_cfg(const DevPass &P, bool glds, int n_loc, const void *x, void *y,
-                      const void *xr, hipStream_t st, unsigned nparts) {
+                      const void *xr, hipStream_t st, unsigned nparts, const DevFlipPass *F) {
   constexpr int NT = 1 << (B - LOGR);
   // DNM_LDS_KB (experiments): request more LDS than the tile needs to cap the
   // number of resident workgroups per CU
@@ -704,6 +833,19 @@ static int launch_cfg(const DevPass &P, bool glds, int n_loc, const void *x, voi
   const bool pack = (P.cache_policy & 256) != 0;          // real-packed records: their own instance (early gathers only)
   // table records / grouped diagonal terms: their own instance (early gathers, plain tile loads)
   const bool tab = P.tab_loop[2] > 0 || P.gbucket[MAXR] > P.gbucket[0];
+  if (F) {      // flip-flop records: their own instances (build_pass gives them to passes with early gathers only)
+    DNM_CHECK(!pack && !tab && gv == 1, "internal: flip-flop records in a pass that cannot run them");
+    using fkern_t = void (*)(const DevPass, const DevFlipPass, const c128 *, c128 *, const c128 *);
+    fkern_t fk = glds ? tile_pass_flip_kernel<B, LOGR, true> : tile_pass_flip_kernel<B, LOGR, false>;
+    static size_t fattr_done[2] = {0, 0};
+    if (fattr_done[glds ? 1 : 0] < lds) {
+      DNM_HIP(hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      fattr_done[glds ? 1 : 0] = lds;
+    }
+    hipLaunchKernelGGL(fk, dim3(grid), dim3(NT), lds, st, P, *F, (const c128 *)x, (c128 *)y, (const c128 *)xr);
+    DNM_HIP(hipGetLastError());
+    return 0;
+  }
   if (pack) k = tile_pass_kernel<B, LOGR, false, 1, true>;
   else if (tab) k = tile_pass_kernel<B, LOGR, false, 1, false, true>;
   else if (glds) k = tile_pass_kernel<B, LOGR, true, 1>;
@@ -731,21 +873,21 @@ bool tile_config_supported(int B, int logR) {
 }
 
 int launch_tile_pass(const DevPass &P, int B, int logR, bool glds, int n_loc, const void *x,
-                     void *y, const void *xr, hipStream_t st, unsigned nparts) {
+                     void *y, const void *xr, hipStream_t st, unsigned nparts, const DevFlipPass *F) {
   DNM_CHECK(n_loc >= B, "tile larger than the local vector");
   switch (B * 16 + logR) {
-    case 8 * 16 + 2: return launch_cfg<8, 2>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 10 * 16 + 2: return launch_cfg<10, 2>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 11 * 16 + 2: return launch_cfg<11, 2>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 12 * 16 + 2: return launch_cfg<12, 2>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 10 * 16 + 3: return launch_cfg<10, 3>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 10 * 16 + 4: return launch_cfg<10, 4>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 11 * 16 + 3: return launch_cfg<11, 3>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 11 * 16 + 4: return launch_cfg<11, 4>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 12 * 16 + 3: return launch_cfg<12, 3>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 12 * 16 + 4: return launch_cfg<12, 4>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 13 * 16 + 3: return launch_cfg<13, 3>(P, glds, n_loc, x, y, xr, st, nparts);
-    case 13 * 16 + 4: return launch_cfg<13, 4>(P, glds, n_loc, x, y, xr, st, nparts);
+    case 8 * 16 + 2: return launch_cfg<8, 2>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 10 * 16 + 2: return launch_cfg<10, 2>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 11 * 16 + 2: return launch_cfg<11, 2>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 12 * 16 + 2: return launch_cfg<12, 2>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 10 * 16 + 3: return launch_cfg<10, 3>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 10 * 16 + 4: return launch_cfg<10, 4>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 11 * 16 + 3: return launch_cfg<11, 3>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 11 * 16 + 4: return launch_cfg<11, 4>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 12 * 16 + 3: return launch_cfg<12, 3>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 12 * 16 + 4: return launch_cfg<12, 4>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 13 * 16 + 3: return launch_cfg<13, 3>(P, glds, n_loc, x, y, xr, st, nparts, F);
+    case 13 * 16 + 4: return launch_cfg<13, 4>(P, glds, n_loc, x, y, xr, st, nparts, F);
   }
   set_error("unsupported tile configuration B=%d logR=%d", B, logR);
   return 1;

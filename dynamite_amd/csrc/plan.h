@@ -181,6 +181,42 @@ struct DevPass {
 };
 constexpr uint32_t MAXDGROUPS = 64;
 
+// ---- flip-flop records ---------------------------------------------------------
+// A mask that flips two bits with real terms whose row coefficient is c where the two bits DIFFER and 0 where they agree
+// (a bond a (XX + YY): c = 2a) needs no sign evaluation: c is one scalar.
+//   tile records (both bits in the tile) run as an EXCHANGE: y[r] += c x[swap(r)], swap(r) = r ^ mask where the bits
+//     differ and r where they agree -- every multiply-add is useful, and the a x[r] too many on the rows whose bits
+//     agree is taken back by the diagonal: the bond's ZZ term d becomes (d - a) ZZ (nothing for an isotropic bond) and
+//     -a joins the constant DevFlipPass::dconst.  Taken only where the diagonal has a ZZ term on the pair to take it
+//     from (decide_flip_bonds / build_flip_pass in mat.cpp): other bonds keep their generic tile records;
+//   gathered records fetch their partners only where the bits differ: decided per workgroup when both bits lie
+//     outside the tile, per row when one of them is a tile bit.
+// DevPass and DevQuad keep describing the WHOLE pass in the generic vocabulary (dnm_mat_export_pass); a pass with
+// flip-flop records runs on a kernel instance of its own that reads the remaining generic records and the reduced
+// diagonal through its own DevPass and the flip-flop records through a DevFlipPass beside it.
+struct DevFlip {
+  uint32_t mask_tile;     // tile records: the two flipped bits in tile coordinates
+  uint32_t mask_pos;      // gathered records: XOR of the partner's POSITION (the vector layout applied to the mask)
+  uint32_t p0, p1;        // tile records: the two bits in tile coordinates (p0 < p1); gathered, both bits outside the
+                          // tile: their index positions; gathered, boundary: p0 = the tile bit in tile coordinates,
+                          // p1 = the index position of the other
+  uint32_t pad[2];        // (no source slot: flip-flop records exist in local passes only, whose gathers read x)
+  double c;
+};
+enum {
+  FL_TILE_T = 0,          // LDS, both bits among the thread bits: one partner address, immediate offsets per row
+  FL_TILE_K,              // LDS, a bit among the k bits
+  FL_GATHER_U,            // gather, both bits outside the tile (workgroup-uniform)
+  FL_GATHER_B,            // gather, one bit in the tile (per-row liveness)
+  FL_COUNT
+};
+struct DevFlipPass {
+  const DevFlip *recs;
+  uint32_t loop[FL_COUNT + 1];   // record range of class i: [loop[i], loop[i+1])
+  uint32_t pad;
+  double dconst;                 // constant of the diagonal (has_diag passes)
+};
+
 // ---- host-side description --------------------------------------------------
 struct PassSpec {
   int B = 0;                       // tile bits

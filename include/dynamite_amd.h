@@ -238,6 +238,15 @@ int dnm_mat_export_pass(const dnm_mat *A, int remote, int idx, void *desc_out, s
  * and their tables ((re, im) pairs); null buffers: the counts alone */
 int dnm_mat_export_tabs(const dnm_mat *A, int remote, int idx, void *tabs_out, size_t tab_bytes, int max_tabs, int *ntabs,
                         double *vals_out, int64_t max_vals, int64_t *nvals);
+/* flip-flop records (plan.h: DevFlip -- two-bit masks whose coefficient is one number where the two bits differ and
+ * nothing where they agree): the records of a pass with their class ranges (FL_COUNT + 1 entries) and the constant of its
+ * diagonal, *nflips = -1 for a pass that runs on its generic records; and what the kernel reads beside them -- the
+ * remaining generic records and the reduced diagonal, in the layouts of dnm_mat_export_pass / _dtile */
+int dnm_mat_export_flip(const dnm_mat *A, int remote, int idx, void *flips_out, size_t flip_bytes, int max_flips,
+                        int *nflips, uint32_t *loops_out, double *dconst);
+int dnm_mat_export_flip_pass(const dnm_mat *A, int remote, int idx, void *desc_out, size_t desc_bytes, void *quads_out,
+                             size_t quad_bytes, int max_quads, int *nquads, double *dtile_out, int64_t max_dtile,
+                             int64_t *ndtile);
 
 /* --- partitioned multiply: replaces the VecScatterCreateToAll all-gather of
  * bcuda_template_2.cu:161-171 with an XOR-partner exchange. ---------------- */
