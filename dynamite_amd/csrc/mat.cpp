@@ -1,7 +1,7 @@
 // C ABI: device helpers, subspace maps, and the shell matrix (create / mult /
 // norm / diagonal / destroy).  See include/dynamite_amd.h for the reference
 // interfaces each entry point replaces.
-#include "mat.h"
+#include "passes.h"
 #include "vec_api.h"
 #include "row_fused.h"
 
@@ -140,705 +140,77 @@ int SubOwned::init(const dnm_subspace *s, bool want_device) {
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// MSC -> row-evaluated index-space form (see plan.h).  Full: identity map.
-// Parity: index = state >> 1; the dropped bit parity(idx)^space is folded
-// into the sign masks (cf. the check_parity branch of sum_term,
-// bpetsc_template_2.c:659-662, 848-854).
-// ---------------------------------------------------------------------------
-static int build_opform(const dnm_mat &A, OpForm *op) {
-  const SubView &l = A.left.host, &r = A.right.host;
-  const bool par = l.type == DNM_PARITY;
-  const int n = par ? l.L - 1 : l.L;
-  op->n = n;
-  op->masks.clear();
-  const uint64_t ones = n >= 64 ? ~0ull : (((uint64_t)1 << n) - 1);
-  for (size_t mi = 0; mi < A.masks.size(); ++mi) {
-    const uint64_t mask = (uint64_t)A.masks[mi];
-    if (par && (parity64(mask) != (l.space ^ r.space))) continue;   // maps outside the right space
-    RowMask rm;
-    rm.mask = par ? (mask >> 1) : mask;
-    for (int64_t t = A.mask_offsets[mi]; t < A.mask_offsets[mi + 1]; ++t) {
-      const uint64_t sg = (uint64_t)A.signs[t];
-      RowTerm rt;
-      rt.is_imag = parity64(mask & sg);           // !TERM_REAL
-      double c = A.real_coeffs[t];
-      uint64_t s2 = sg;
-      if (par) {
-        s2 = sg >> 1;
-        if (sg & 1) {
-          s2 ^= ones;
-          if (r.space) c = -c;
-        }
-      }
-      // column-evaluated -> row-evaluated: col = row ^ mask
-      if (parity64(rm.mask & s2)) c = -c;
-      rt.sign = s2;
-      rt.coeff = c;
-      rm.terms.push_back(rt);
-    }
-    if (rm.mask == 0) {
-      RowMask im;
-      im.mask = 0;
-      im.zero_mask_offdiag = true;
-      std::vector<RowTerm> re;
-      for (const RowTerm &t : rm.terms) (t.is_imag ? im.terms : re).push_back(t);
-      rm.terms.swap(re);
-      if (!im.terms.empty()) op->masks.push_back(std::move(im));
-      if (rm.terms.empty()) continue;
-    }
-    op->masks.push_back(std::move(rm));
-  }
-  std::stable_sort(op->masks.begin(), op->masks.end(),
-            [](const RowMask &a, const RowMask &b) { return a.mask < b.mask; });
+// (the pass builder -- build_opform ... build_flip_pass -- lives in passes.cpp)
+template <class T>
+static int upload_to(DevBuf &buf, const std::vector<T> &v, const T **dev) {
+  DNM_TRY(buf.upload(v.data(), v.size() * sizeof(T)));
+  *dev = (const T *)buf.p;
   return 0;
 }
-
-static uint32_t compress_to_tile(uint64_t bits, const PassSpec &ps) {
-  uint32_t out = 0;
-  int off = 0;
-  for (int j = 0; j < ps.nseg; ++j) {
-    uint64_t seg = (bits >> ps.seg_pos[j]) & (((uint64_t)1 << ps.seg_len[j]) - 1);
-    out |= (uint32_t)seg << off;
-    off += ps.seg_len[j];
-  }
-  return out;
-}
-
-// Real-packed form of a real operator (DNM_MAT_REAL_PACKED): index r = 2 j + b, element j of a vector holds the
-// amplitudes b = 0 (real part) and b = 1 (imaginary part).  A term (mask m, sign s, coefficient c) contributes
-// c (-1)^popcount(r & s) x[r ^ m] to y[r]; with m' = m >> 1, s' = s >> 1, f = m & 1:
-//   y[j].lane(b) += c (-1)^popcount(j & s') (-1)^(b (s & 1)) x[j ^ m'].lane(b ^ f)
-// -- one coefficient per lane.  The form keeps the record layout: a term's is_imag names its lane, the records of a
-// mask carry both lanes (slots 0, 1: lane 0; slots 2, 3: lane 1) and RowMask::pack_flip = f.  Diagonal terms whose
-// sign reaches bit 0 differ between the lanes: they become a mask-0 off-diagonal entry (partner = the element itself).
-static int pack_opform(OpForm *op) {
-  DNM_CHECK(op->n >= 2, "real-packed form needs at least two index bits");
-  std::vector<RowMask> out;
-  for (const RowMask &rm : op->masks) {
-    for (const RowTerm &t : rm.terms) DNM_CHECK(!t.is_imag, "operator has an imaginary matrix element: no real-packed form");
-    DNM_CHECK(!rm.zero_mask_offdiag, "operator has an imaginary matrix element: no real-packed form");
-    RowMask lanes;
-    lanes.mask = rm.mask >> 1;
-    lanes.pack_flip = (rm.mask & 1) != 0;
-    if (rm.mask == 0) {
-      RowMask diag;                       // what both lanes share stays the diagonal
-      diag.mask = 0;
-      lanes.zero_mask_offdiag = true;
-      for (const RowTerm &t : rm.terms) {
-        if (!(t.sign & 1)) { diag.terms.push_back({t.sign >> 1, t.coeff, 0}); continue; }
-        lanes.terms.push_back({t.sign >> 1, t.coeff, 0});
-        lanes.terms.push_back({t.sign >> 1, -t.coeff, 1});
-      }
-      if (!diag.terms.empty()) out.push_back(std::move(diag));
-      if (!lanes.terms.empty()) out.push_back(std::move(lanes));
-      continue;
-    }
-    lanes.zero_mask_offdiag = lanes.mask == 0;       // the mask flipped bit 0 only: the element's own other lane
-    bool same = !lanes.pack_flip;                    // bit 0 neither flipped nor seen by a sign: both lanes get the same
-    for (const RowTerm &t : rm.terms) same = same && !(t.sign & 1);      // real coefficient -- an ordinary real record
-    for (const RowTerm &t : rm.terms) {
-      lanes.terms.push_back({t.sign >> 1, t.coeff, 0});
-      if (!same) lanes.terms.push_back({t.sign >> 1, (t.sign & 1) ? -t.coeff : t.coeff, 1});
-    }
-    out.push_back(std::move(lanes));
-  }
-  std::stable_sort(out.begin(), out.end(), [](const RowMask &a, const RowMask &b) {
-    if (a.mask != b.mask) return a.mask < b.mask;
-    return (int)a.zero_mask_offdiag < (int)b.zero_mask_offdiag;        // the diagonal first
-  });
-  op->masks.swap(out);
-  op->n -= 1;
-  op->packed = true;
-  return 0;
-}
-
-// A mask of many terms as table records (plan.h: DevTab)?  Its terms grouped by their sign mask outside the flipped bits
-// (`zs`: one record and one table per group) -- taken where that is cheaper than records of four terms (about 45 against
-// 76 vector instructions each for four rows; DNM_TAB_RECORDS=0: never).
-static bool table_form(const OpForm &op, const RowMask &m, std::vector<uint64_t> *zs) {
-  const char *tabs_env = knob("DNM_TAB_RECORDS");
-  if (tabs_env && tabs_env[0] == '0') return false;
-  const int nb = __builtin_popcountll(m.mask);
-  if (op.packed || m.pack_flip || nb < 1 || nb > MAXTABBITS || m.terms.size() < 5) return false;
-  size_t nre = 0, nim = 0;
-  zs->clear();
-  for (const RowTerm &t : m.terms) {
-    (t.is_imag ? nim : nre)++;
-    const uint64_t z = t.sign & ~m.mask;
-    if (std::find(zs->begin(), zs->end(), z) == zs->end()) zs->push_back(z);
-  }
-  // (masks of one record stay records: a single flip's X + iY -- the harness's long_range -- as a table of two entries made
-  // that operator SLOWER, 7.11 -> 7.59 ms at L=28: a table record has its own fixed costs, the staging of the tables and the
-  // kernel instance of 8 rows per thread among them)
-  const size_t nq = std::max((nre + 1) / 2, (nim + 1) / 2);
-  return nq >= 2 && zs->size() * 45 < nq * 76;
-}
-
-// the operator's diagonal (its mask-0 entry of real terms), or null
-static const RowMask *diagonal_mask(const OpForm &op) {
-  const RowMask *dm = nullptr;
-  for (const RowMask &m : op.masks) if (m.mask == 0 && !m.zero_mask_offdiag) dm = &m;
-  return dm;
-}
-
-// A mask as a flip-flop record (plan.h: DevFlip)?  It flips exactly two bits, its terms are real and see no other bit,
-// and their sum is c on the rows whose two bits differ and nothing on the others: a bond a (XX + YY), c = 2a.  (A Parity
-// mask whose folded bit spreads a sign mask over the index does not qualify, nor does XX alone or a DM term.)
-static FlipBond flip_classify(const RowMask &m) {
-  FlipBond fb;
-  if (__builtin_popcountll(m.mask) != 2 || m.zero_mask_offdiag || m.pack_flip) return fb;
-  fb.b0 = __builtin_ctzll(m.mask);
-  fb.b1 = 63 - __builtin_clzll(m.mask);
-  double f[4] = {0.0, 0.0, 0.0, 0.0};      // the coefficient by (bit b0, bit b1) of the row
-  for (const RowTerm &t : m.terms) {
-    if (t.is_imag || (t.sign & ~m.mask)) return fb;
-    for (int v = 0; v < 4; ++v) {
-      const int par = ((v & 1) && ((t.sign >> fb.b0) & 1)) ^ ((v & 2) && ((t.sign >> fb.b1) & 1));
-      f[v] += par ? -t.coeff : t.coeff;
-    }
-  }
-  if (f[0] != 0.0 || f[3] != 0.0 || f[1] != f[2] || f[1] == 0.0) return fb;
-  fb.c = f[1];
-  fb.ok = true;
-  return fb;
-}
-
-// The tables of the table records of a pass (plan.h: DevTab)
-struct PassTabs {
-  std::vector<DevTab> tile, gather;
-  std::vector<double> vals;
-};
-
-// The records of a pass from a list of diagonal terms (null: none) and the masks that `skip` does not name (empty: all):
-// once for the generic description of the pass (the operator's own diagonal, every mask), once more for the kernel when
-// some of the operator's masks run as flip-flop records (plan.h: DevFlip; build_flip_pass below).  Fills the record
-// ranges of d; the geometry and everything else in d is the caller's.
-static int emit_records(const dnm_mat &A, const PassSpec &ps, int logR, DevPass &d, std::vector<DevQuad> &quads,
-                        std::vector<double> &h_dtile, PassTabs &T, const std::vector<RowTerm> *dterms,
-                        const std::vector<char> &skip) {
-  const OpForm &op = A.op;
-  const int B = ps.B, lognt = B - logR, R = 1 << logR;
-  const int n_eff = ps.n_eff ? ps.n_eff : A.plan.n_loc;
-  const uint64_t tb = ps.tile_bits();
-  std::vector<DevTab> &tabs_tile = T.tile, &tabs_gather = T.gather;
-  std::vector<double> &tabvals = T.vals;
-  auto empty_quad = [&]() {
-    DevQuad q;
-    memset(&q, 0, sizeof(q));
-    return q;
-  };
-  auto set_slot = [&](DevQuad &q, int slot, const RowTerm &t) {
-    q.sign_ext[slot] = t.sign & ~tb;
-    q.sign_tile[slot] = compress_to_tile(t.sign & tb, ps);
-    q.coeff[slot] = t.coeff;
-  };
-  // pack a list of (real) diagonal terms four to a record
-  auto push_diag_list = [&](const std::vector<RowTerm> &lst) {
-    for (size_t i = 0; i < lst.size(); i += 4) {
-      DevQuad q = empty_quad();
-      for (size_t j = i; j < lst.size() && j < i + 4; ++j) {
-        set_slot(q, (int)(j - i), lst[j]);
-        q.nslots = (uint32_t)(j - i + 1);
-      }
-      quads.push_back(q);
-    }
-  };
-
-  if (ps.has_diag) {
-    if (dterms) {
-      d.has_diag = 1;
-      std::vector<RowTerm> lst;
-      for (const RowTerm &t : *dterms)
-        if (compress_to_tile(t.sign & tb, ps) == 0) lst.push_back(t);
-      d.dext_begin = (uint32_t)quads.size();
-      push_diag_list(lst);
-      d.dext_end = (uint32_t)quads.size();
-      // terms inside the tile only: tabulated per tile coordinate (DNM_DIAG_TABLE=0: bucket lists as before)
-      const char *dte = knob("DNM_DIAG_TABLE");
-      const bool use_table = !(dte && dte[0] == '0') && B <= 13;
-      if (use_table) h_dtile.assign((size_t)1 << B, 0.0);
-      // terms that see the tile AND bits outside it, grouped by their sign mask inside the tile (DevPass::gbucket): groups of
-      // three terms or more are summed over the outside bits once per workgroup (DNM_DIAG_GROUPS=0: every term per thread)
-      std::vector<std::pair<uint32_t, std::vector<RowTerm>>> groups;
-      {
-        const char *dge = knob("DNM_DIAG_GROUPS");
-        const bool grouping = !(dge && dge[0] == '0') && !op.packed && !(A.flags & DNM_MAT_USE_GLDS);
-        std::vector<std::pair<uint32_t, std::vector<RowTerm>>> all;
-        if (grouping)
-          for (const RowTerm &t : *dterms) {
-            const uint32_t st = compress_to_tile(t.sign & tb, ps);
-            if (st == 0 || (t.sign & ~tb) == 0) continue;
-            auto it = std::find_if(all.begin(), all.end(), [&](const auto &g) { return g.first == st; });
-            if (it == all.end()) { all.push_back({st, {}}); it = all.end() - 1; }
-            it->second.push_back(t);
-          }
-        std::stable_sort(all.begin(), all.end(), [](const auto &a, const auto &b) { return a.second.size() > b.second.size(); });
-        for (auto &g : all)
-          if (g.second.size() >= 3 && groups.size() < MAXDGROUPS) groups.push_back(std::move(g));
-      }
-      auto grouped = [&](uint32_t st) {
-        return std::any_of(groups.begin(), groups.end(), [&](const auto &g) { return g.first == st; });
-      };
-      for (int j = 0; j < R; ++j) {
-        lst.clear();
-        for (const RowTerm &t : *dterms) {
-          uint32_t st = compress_to_tile(t.sign & tb, ps);
-          if (st == 0 || (int)(st >> lognt) != j) continue;
-          if (use_table && (t.sign & ~tb) == 0) {
-            for (uint32_t tc = 0; tc < (1u << B); ++tc)
-              h_dtile[tc] += (__builtin_popcount(tc & st) & 1) ? -t.coeff : t.coeff;
-          } else if ((t.sign & ~tb) != 0 && grouped(st)) {
-            continue;
-          } else {
-            lst.push_back(t);
-          }
-        }
-        d.dbucket[j] = (uint32_t)quads.size();
-        push_diag_list(lst);
-      }
-      for (int j = R; j <= MAXR; ++j) d.dbucket[j] = (uint32_t)quads.size();
-      // the groups: their term records (the outside part of every sign mask), then one record per group, by k bucket
-      std::vector<std::pair<uint32_t, uint32_t>> where(groups.size());
-      for (size_t g = 0; g < groups.size(); ++g) {
-        std::vector<RowTerm> outside = groups[g].second;
-        for (RowTerm &t : outside) t.sign &= ~tb;
-        where[g].first = (uint32_t)quads.size();
-        push_diag_list(outside);
-        where[g].second = (uint32_t)quads.size() - where[g].first;
-      }
-      for (int j = 0; j < R; ++j) {
-        d.gbucket[j] = (uint32_t)quads.size();
-        for (size_t g = 0; g < groups.size(); ++g) {
-          if ((int)(groups[g].first >> lognt) != j) continue;
-          DevQuad q = empty_quad();
-          q.sign_tile[0] = groups[g].first;
-          q.mask_loc = where[g].first;
-          q.src = where[g].second;
-          q.nslots = 1;
-          quads.push_back(q);
-        }
-      }
-      for (int j = R; j <= MAXR; ++j) d.gbucket[j] = (uint32_t)quads.size();
-    }
-  }
-
-  // off-diagonal masks: records of <= 2 real + <= 2 imaginary terms, sorted into
-  // the kernel's loops (tile/gather x k-variant x real/complex)
-  struct Rec { int loop; DevQuad q; };
-  std::vector<Rec> recs;
-  // masks of many terms as table records (table_form above)
-  auto push_tabs = [&](const RowMask &m, uint64_t mloc, bool gather, int src) -> bool {
-    std::vector<uint64_t> zs;
-    if (!table_form(op, m, &zs)) return false;
-    const int nb = __builtin_popcountll(m.mask);
-    int pb[MAXTABBITS];
-    for (int q = 0, pos = 0; pos < 64; ++pos)
-      if ((m.mask >> pos) & 1ull) pb[q++] = pos;
-    for (uint64_t z : zs) {
-      DevTab T;
-      memset(&T, 0, sizeof(T));
-      T.mask_tile = compress_to_tile(mloc & tb, ps);
-      T.mask_loc = (uint32_t)mloc;
-      T.src = (uint32_t)src;
-      T.nbits = (uint32_t)nb;
-      const uint32_t zt = compress_to_tile(z & tb, ps);
-      T.z_tile = zt & ((1u << lognt) - 1u);
-      T.z_ext = z & ~tb;
-      T.first = (uint32_t)(tabvals.size() / 2);
-      for (int k = 0; k < R; ++k)
-        if (__builtin_popcount((uint32_t)k & (zt >> lognt)) & 1) T.ksign |= 1u << k;
-      for (int q = 0; q < nb; ++q) {
-        if ((tb >> pb[q]) & 1ull) {
-          const int tpos = __builtin_ctz(compress_to_tile((uint64_t)1 << pb[q], ps));
-          if (tpos < lognt) {
-            T.tpos |= (uint32_t)tpos << (8 * q);
-            T.twid |= 1u << (8 * q);
-          } else {
-            T.flags |= 1u;
-            for (int k = 0; k < R; ++k)
-              if ((k >> (tpos - lognt)) & 1) T.ik |= (uint64_t)1 << (4 * k + q);
-          }
-        } else {
-          T.epos |= (uint32_t)pb[q] << (8 * q);
-          T.ewid |= 1u << (8 * q);
-        }
-      }
-      for (int j = 0; j < (1 << nb); ++j) {
-        uint64_t rowbits = 0;
-        for (int q = 0; q < nb; ++q)
-          if ((j >> q) & 1) rowbits |= (uint64_t)1 << pb[q];
-        double re = 0.0, im = 0.0;
-        for (const RowTerm &t : m.terms) {
-          if ((t.sign & ~m.mask) != z) continue;
-          const double c = (__builtin_popcountll(rowbits & t.sign & m.mask) & 1) ? -t.coeff : t.coeff;
-          (t.is_imag ? im : re) += c;
-        }
-        tabvals.push_back(re);
-        tabvals.push_back(im);
-      }
-      if (z == zs.back()) T.flags |= 2u;        // (the groups of a mask: consecutive records, one fetch of the partners)
-      (gather ? tabs_gather : tabs_tile).push_back(T);
-    }
-    return true;
-  };
-  auto push_mask = [&](int idx, bool gather, int src) {
-    const RowMask &m = op.masks[idx];
-    const uint64_t mloc = m.mask & (((uint64_t)1 << n_eff) - 1);
-    if (!gather) DNM_CHECK((mloc & ~tb) == 0, "internal: tile mask leaves the tile");
-    if (push_tabs(m, mloc, gather, src)) return 0;
-    std::vector<const RowTerm *> re, im;
-    for (const RowTerm &t : m.terms) (t.is_imag ? im : re).push_back(&t);
-    size_t ir = 0, ii = 0;
-    while (ir < re.size() || ii < im.size()) {
-      DevQuad q = empty_quad();
-      q.mask_tile = compress_to_tile(mloc & tb, ps);
-      q.mask_loc = (uint32_t)mloc;
-      q.src = (uint32_t)src;
-      q.nslots = m.pack_flip ? 1u : 0u;       // real-packed operators: a lane reads the partner's other lane
-      bool kvar = false, cplx = false;
-      for (int s = 0; s < 2 && ir < re.size(); ++s, ++ir) {
-        set_slot(q, s, *re[ir]);
-        kvar |= (q.sign_tile[s] >> lognt) != 0;
-      }
-      for (int s = 2; s < 4 && ii < im.size(); ++s, ++ii) {
-        set_slot(q, s, *im[ii]);
-        kvar |= (q.sign_tile[s] >> lognt) != 0;
-        cplx = true;
-      }
-      int loop;
-      if (gather) loop = kvar ? (cplx ? LP_GATHER_KVAR_CPLX : LP_GATHER_KVAR_REAL) : (cplx ? LP_GATHER_CPLX : LP_GATHER_REAL);
-      else if (kvar) loop = cplx ? LP_TILE_KVAR_CPLX : LP_TILE_KVAR_REAL;
-      else if (cplx) loop = LP_TILE_CPLX;
-      else loop = (q.mask_tile >> lognt) == 0 ? LP_TILE_REAL_K0 : LP_TILE_REAL;
-      recs.push_back({loop, q});
-    }
-    return 0;
-  };
-  for (int idx : ps.tile_masks)
-    if (skip.empty() || !skip[idx]) DNM_TRY(push_mask(idx, false, 0));
-  for (size_t i = 0; i < ps.gather_masks.size(); ++i)
-    if (skip.empty() || !skip[ps.gather_masks[i]]) DNM_TRY(push_mask(ps.gather_masks[i], true, ps.gather_src[i]));
-  for (int lp = 0; lp < LP_COUNT; ++lp) {
-    d.loop[lp] = (uint32_t)quads.size();
-    for (const Rec &r : recs) if (r.loop == lp) quads.push_back(r.q);
-  }
-  d.loop[LP_COUNT] = (uint32_t)quads.size();
-  d.nquads = (int32_t)quads.size();
-  return 0;
-}
-
-static int build_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
-  const OpForm &op = A.op;
-  const Plan &pl = A.plan;
-  const int B = ps.B;
-  int logR = ps.logR ? ps.logR : pl.cfg.logR;
-  {
-    // passes with table records: rows per thread of their own (DNM_TAB_LOG_ROWS; the per-record work of a thread -- table
-    // index, parity -- is shared by its rows)
-    std::vector<uint64_t> zs;
-    bool any = false;
-    for (int idx : ps.tile_masks) any = any || table_form(op, op.masks[idx], &zs);
-    for (int idx : ps.gather_masks) any = any || table_form(op, op.masks[idx], &zs);
-    int want = 3;
-    if (const char *e = knob("DNM_TAB_LOG_ROWS")) want = atoi(e);
-    if (any && want > logR && tile_config_supported(B, want)) logR = want;
-  }
-  {
-    // the thread part of a position has to fit a 32-bit byte offset (DevPass::pos_tmask): a tile that reaches above
-    // bit 27 gives its top bits to the rows of a thread
-    auto top_thread_pos = [&](int lr) {
-      int c = 0, top = -1;
-      for (int j = 0; j < ps.nseg; ++j)
-        for (int i = 0; i < ps.seg_len[j]; ++i, ++c)
-          if (c < B - lr) top = std::max(top, ps.seg_pos[j] + i);
-      return top;
-    };
-    while (top_thread_pos(logR) >= 28 && tile_config_supported(B, logR + 1)) ++logR;
-  }
-  const int lognt = B - logR, R = 1 << logR;
-  const int n_eff = ps.n_eff ? ps.n_eff : pl.n_loc;     // index bits this pass sweeps
-  const uint64_t tb = ps.tile_bits();
-  DevPass &d = out->desc;
-  memset(&d, 0, sizeof(d));
-  d.nseg = ps.nseg;
-  int off = 0;
-  for (int j = 0; j < ps.nseg; ++j) {
-    d.seg_off[j] = off;
-    d.seg_len[j] = ps.seg_len[j];
-    d.seg_pos[j] = ps.seg_pos[j];
-    off += ps.seg_len[j];
-  }
-  DNM_CHECK(off == B, "internal: tile segments do not add up to B");
-  // block-id bits -> local index bits outside the tile.  Order (low to high):
-  // three selector bits (workgroup b runs on XCD b % 8), the XCD-group bits, the rest.
-  {
-    std::vector<int> order;
-    uint64_t gb = ps.glen ? ((((uint64_t)1 << ps.glen) - 1) << ps.gpos) : 0;
-    std::vector<int> rest;
-    for (int pos = 0; pos < n_eff; ++pos)
-      if (!((tb >> pos) & 1) && !((gb >> pos) & 1)) rest.push_back(pos);
-    size_t nsel = ps.glen ? std::min<size_t>(3, rest.size()) : 0;
-    for (size_t i = 0; i < nsel; ++i) order.push_back(rest[i]);
-    for (int pos = ps.gpos; pos < ps.gpos + ps.glen; ++pos) order.push_back(pos);
-    for (size_t i = nsel; i < rest.size(); ++i) order.push_back(rest[i]);
-    if (const char *e = knob("DNM_ORDER_WINDOW")) {     // experiments: explicit block-id bit order (low to high)
-      if (ps.nseg > 1 && ps.partner < 0) {
-        std::vector<int> o;
-        for (const char *q = e; *q;) {
-          o.push_back(atoi(q));
-          while (*q && *q != ',') ++q;
-          if (*q == ',') ++q;
-        }
-        std::vector<int> a = o, b2 = order;
-        std::sort(a.begin(), a.end());
-        std::sort(b2.begin(), b2.end());
-        DNM_CHECK(a == b2, "DNM_ORDER_WINDOW is not a permutation of the block bits");
-        order = o;
-      }
-    }
-    DNM_CHECK((int)order.size() == n_eff - B, "internal: block bits do not add up");
-    int nb = 0;
-    for (size_t i = 0; i < order.size();) {
-      size_t j = i + 1;
-      while (j < order.size() && order[j] == order[j - 1] + 1) ++j;
-      DNM_CHECK(nb < MAXBSEG, "internal: too many block segments");
-      d.bseg_off[nb] = (int32_t)i;
-      d.bseg_len[nb] = (int32_t)(j - i);
-      d.bseg_pos[nb] = order[i];
-      ++nb;
-      i = j;
-    }
-    d.nbseg = nb;
-  }
-  d.sign_base = ((uint64_t)pl.rank << pl.n_loc) | ps.sign_extra;
-  d.n_eff = n_eff;
-  d.tile_bits = B;
-  d.log_rows = logR;
-  DNM_CHECK(tile_config_supported(B, logR), "unsupported tile configuration B=%d logR=%d", B, logR);
-  d.accumulate = ps.accumulate ? 1 : 0;
-  d.has_diag = 0;
-  d.cache_policy = pl.cfg.cache_policy | (op.packed ? 256 : 0);      // bit 8: real-packed records (kernel instance)
-  {
-    const int S = pl.cfg.swz;
-    DNM_CHECK(S == 0 || (S >= 5 && S <= 24), "swizzle shift %d out of range", S);
-    d.swz_shift = S;
-    auto sw = [S](uint64_t v) -> uint32_t {
-      return S ? (uint32_t)(((v >> S) & (((uint64_t)1 << (S - 4)) - 1)) << 4) : 0u;
-    };
-    d.swz_xor_y = sw((uint64_t)ps.y_off);
-    d.swz_xor_src = sw((uint64_t)ps.src_off);
-    // position bits the thread part of the tile coordinate reaches (the kernel keeps them in a 32-bit byte offset)
-    uint64_t tm = 0;
-    int c = 0;
-    for (int j = 0; j < ps.nseg; ++j)
-      for (int i = 0; i < ps.seg_len[j]; ++i, ++c)
-        if (c < lognt) tm |= ((uint64_t)1 << (ps.seg_pos[j] + i)) | sw((uint64_t)1 << (ps.seg_pos[j] + i));
-    DNM_CHECK((tm >> 28) == 0, "internal: thread bits of the tile above bit 27 (tile %llx, %d rows per thread)",
-              (unsigned long long)tb, R);
-    d.pos_tmask = (uint32_t)tm;
-  }
-
-  PassTabs T;
-  std::vector<DevQuad> quads;
-  const RowMask *dm = diagonal_mask(op);
-  DNM_TRY(emit_records(A, ps, logR, d, quads, out->h_dtile, T, dm ? &dm->terms : nullptr, std::vector<char>()));
-  d.need_tile = (d.has_diag || !ps.tile_masks.empty()) ? 1 : 0;
-  d.tab_loop[0] = 0;
-  d.tab_loop[1] = (uint32_t)T.tile.size();
-  d.tab_loop[2] = (uint32_t)(T.tile.size() + T.gather.size());
-  out->h_tabs = T.tile;
-  out->h_tabs.insert(out->h_tabs.end(), T.gather.begin(), T.gather.end());
-  out->h_tabvals = T.vals;
-  d.tabs = nullptr;
-  d.tabvals = nullptr;
-  if (!out->h_tabs.empty() && !A.host_only) {
-    DNM_TRY(out->tabs.upload(out->h_tabs.data(), out->h_tabs.size() * sizeof(DevTab)));
-    DNM_TRY(out->tabvals.upload(out->h_tabvals.data(), out->h_tabvals.size() * sizeof(double)));
-    d.tabs = (const DevTab *)out->tabs.p;
-    d.tabvals = (const double *)out->tabvals.p;
-  }
-  out->h_quads = quads;
-  if (!A.host_only) DNM_TRY(out->quads.upload(quads.data(), quads.size() * sizeof(DevQuad)));
-  d.quads = (const DevQuad *)out->quads.p;
-  d.dtile = nullptr;
-  if (!out->h_dtile.empty() && !A.host_only) {
-    DNM_TRY(out->dtile.upload(out->h_dtile.data(), out->h_dtile.size() * sizeof(double)));
-    d.dtile = (const double *)out->dtile.p;
-  }
-  out->partner = ps.partner;
-  out->n_eff = n_eff;
-  out->y_off = ps.y_off;
-  out->src_off = ps.src_off;
-  return 0;
-}
-
-// The masks of an operator that run as flip-flop records (plan.h: DevFlip), decided ONCE per operator, after its passes
-// have been built generically: A->flip_bonds[i] for op.masks[i].  None (DNM_FLIPFLOP=0, or an operator that needs another
-// kernel instance: real-packed, late gathers, or any local pass whose generic form has table records or grouped diagonal
-// terms -- read off the passes as emit_records built them) leaves the vector empty.
-//   gathered masks: no condition beyond flip_classify (nothing changes but the record);
-//   tile masks run as exchanges, which take a = c / 2 off the ZZ term on the bond's pair: taken only where the diagonal HAS
-//   that term.  The reduced diagonal then has no sign mask that the operator's own lacks, so whatever emit_records groups
-//   of it is a subset of what it grouped before -- a pass without grouped terms stays without.  (An XY bond would ADD a
-//   term per bond, across the tile boundary of the diagonal pass one that every thread evaluates, three of them on one
-//   spin a group: such bonds keep their generic tile records.)
-static void decide_flip_bonds(dnm_mat *A) {
-  const OpForm &op = A->op;
-  const Plan &pl = A->plan;
-  A->flip_bonds.clear();
-  const char *e = knob("DNM_FLIPFLOP");
-  if ((e && e[0] == '0') || op.packed || !(pl.cfg.cache_policy & 32)) return;
-  const RowMask *dm = diagonal_mask(op);
-  bool diag_pass = false;
-  for (size_t i = 0; i < pl.local.size(); ++i) {
-    const DevPass &d = A->local_passes[i]->desc;
-    if (d.tab_loop[2] > 0 || d.gbucket[MAXR] > d.gbucket[0]) return;
-    diag_pass = diag_pass || d.has_diag;
-  }
-  std::vector<FlipBond> bonds(op.masks.size());
-  bool any = false;
-  for (const PassSpec &ps : pl.local) {
-    for (int idx : ps.tile_masks) {
-      FlipBond fb = flip_classify(op.masks[idx]);
-      const uint64_t pair = op.masks[idx].mask;
-      fb.exch = fb.ok && diag_pass && dm &&
-                std::any_of(dm->terms.begin(), dm->terms.end(), [&](const RowTerm &t) { return t.sign == pair; });
-      fb.ok = fb.exch;
-      bonds[idx] = fb;
-      any = any || fb.ok;
-    }
-    for (size_t i = 0; i < ps.gather_masks.size(); ++i) {
-      if (ps.gather_src[i] != 0) continue;
-      bonds[ps.gather_masks[i]] = flip_classify(op.masks[ps.gather_masks[i]]);
-      any = any || bonds[ps.gather_masks[i]].ok;
-    }
-  }
-  if (any) A->flip_bonds.swap(bonds);
-}
-
-// What the kernel runs on when the operator has flip-flop records: the records of this local pass, the generic records
-// that remain and the diagonal as the exchanges leave it (out->fdesc, built by the same emit_records)
-static int build_flip_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
-  const OpForm &op = A.op;
-  const Plan &pl = A.plan;
-  const std::vector<FlipBond> &bonds = A.flip_bonds;
-  if (bonds.empty()) return 0;
-  const DevPass &d = out->desc;
-  const int lognt = d.tile_bits - d.log_rows;
-  const uint64_t tb = ps.tile_bits();
-  std::vector<char> skip(op.masks.size(), 0);
-  std::vector<DevFlip> fl[FL_COUNT];
-  const int S = pl.cfg.swz;
-  auto add_flip = [&](int idx, bool gather) {
-    const FlipBond &fb = bonds[idx];
-    if (!fb.ok) return;
-    DevFlip f;
-    memset(&f, 0, sizeof(f));
-    f.c = fb.c;
-    const uint64_t b0 = (uint64_t)1 << fb.b0, b1 = (uint64_t)1 << fb.b1;
-    int cls;
-    if (!gather) {
-      f.mask_tile = compress_to_tile(b0 | b1, ps);
-      f.p0 = (uint32_t)__builtin_ctz(f.mask_tile);
-      f.p1 = 31u - (uint32_t)__builtin_clz(f.mask_tile);
-      cls = (int)f.p1 < lognt ? FL_TILE_T : FL_TILE_K;
-    } else {
-      const uint64_t mloc = b0 | b1;
-      f.mask_pos = (uint32_t)(S ? (mloc ^ (((mloc >> S) & (((uint64_t)1 << (S - 4)) - 1)) << 4)) : mloc);
-      if (!(tb & mloc)) {
-        f.p0 = (uint32_t)fb.b0;
-        f.p1 = (uint32_t)fb.b1;
-        cls = FL_GATHER_U;
-      } else {
-        const bool low_in = (tb & b0) != 0;        // (a gather mask has a bit outside the tile)
-        f.p0 = (uint32_t)__builtin_ctz(compress_to_tile(low_in ? b0 : b1, ps));
-        f.p1 = (uint32_t)(low_in ? fb.b1 : fb.b0);
-        cls = FL_GATHER_B;
-      }
-    }
-    fl[cls].push_back(f);
-    skip[idx] = 1;
-  };
-  for (int idx : ps.tile_masks) add_flip(idx, false);
-  for (int idx : ps.gather_masks) add_flip(idx, true);
-  // the diagonal as the exchanges leave it: per bond that runs as an exchange (in whichever local pass) the ZZ term on
-  // its pair loses a = c / 2 (an isotropic bond's is gone), and -a joins the constant
-  const RowMask *dm = diagonal_mask(op);
-  std::vector<RowTerm> dterms;
-  if (dm) dterms = dm->terms;
-  double dconst = 0.0;
-  bool diag_changed = false;
-  if (ps.has_diag)
-    for (size_t idx = 0; idx < bonds.size(); ++idx) {
-      if (!bonds[idx].exch) continue;
-      const double a = 0.5 * bonds[idx].c;
-      const uint64_t pair = op.masks[idx].mask;
-      auto it = std::find_if(dterms.begin(), dterms.end(), [&](const RowTerm &t) { return t.sign == pair; });
-      DNM_CHECK(it != dterms.end(), "internal: an exchange without a ZZ term on its pair");
-      if (it->coeff == a) dterms.erase(it);
-      else it->coeff -= a;
-      dconst -= a;
-      diag_changed = true;
-    }
-  size_t nflip = 0;
-  for (int c = 0; c < FL_COUNT; ++c) nflip += fl[c].size();
-  if (nflip == 0 && !diag_changed) return 0;
-  out->fdesc = d;
-  PassTabs T;
-  DNM_TRY(emit_records(A, ps, d.log_rows, out->fdesc, out->h_fquads, out->h_fdtile, T, dm ? &dterms : nullptr, skip));
-  // (what decide_flip_bonds relies on: the reduced pass needs no other kernel instance than the flip-flop one)
-  DNM_CHECK(T.tile.empty() && T.gather.empty() && out->fdesc.gbucket[MAXR] == out->fdesc.gbucket[0],
-            "internal: the flip-flop form of a pass has table records or grouped diagonal terms");
-  DevFlipPass &fp = out->flip;
-  memset(&fp, 0, sizeof(fp));
-  for (int c = 0; c < FL_COUNT; ++c) {
-    fp.loop[c] = (uint32_t)out->h_flips.size();
-    out->h_flips.insert(out->h_flips.end(), fl[c].begin(), fl[c].end());
-  }
-  fp.loop[FL_COUNT] = (uint32_t)out->h_flips.size();
-  if (out->h_flips.empty()) out->h_flips.push_back(DevFlip{});      // (a pass that only carries the reduced diagonal)
-  fp.dconst = dconst;
-  out->fdesc.quads = nullptr;
-  out->fdesc.dtile = nullptr;
-  if (!A.host_only) {
-    DNM_TRY(out->flips.upload(out->h_flips.data(), out->h_flips.size() * sizeof(DevFlip)));
-    DNM_TRY(out->fquads.upload(out->h_fquads.data(), out->h_fquads.size() * sizeof(DevQuad)));
-    fp.recs = (const DevFlip *)out->flips.p;
-    out->fdesc.quads = (const DevQuad *)out->fquads.p;
-    if (!out->h_fdtile.empty()) {
-      DNM_TRY(out->fdtile.upload(out->h_fdtile.data(), out->h_fdtile.size() * sizeof(double)));
-      out->fdesc.dtile = (const double *)out->fdtile.p;
-    }
-  }
+int PassRecords::upload() {
+  DNM_TRY(upload_to(d_quads, quads, &desc.quads));
+  if (!dtile.empty()) DNM_TRY(upload_to(d_dtile, dtile, &desc.dtile));
+  if (!tabs.empty()) DNM_TRY(upload_to(d_tabs, tabs, &desc.tabs));
+  if (!tabs.empty()) DNM_TRY(upload_to(d_tabvals, tabvals, &desc.tabvals));
+  // (a pass that only carries the reduced diagonal has no flip-flop record: the kernel still takes a non-null pointer)
+  if (is_reduced) DNM_TRY(upload_to(d_flips, flips.empty() ? std::vector<DevFlip>(1) : flips, &flip.recs));
   return 0;
 }
 
 static hipStream_t S(void *stream) { return (hipStream_t)stream; }
 
-// d: the pass descriptor with this call's fields filled in; p: the pass it was copied from
-static int launch_pass(const dnm_mat *A, const PassOnDevice &p, const DevPass &d, const void *x, void *y,
-                       const void *xr, hipStream_t st, unsigned nparts = 1) {
-  const bool glds = (A->flags & DNM_MAT_USE_GLDS) != 0;
-  if (p.h_flips.empty()) return launch_tile_pass(d, d.tile_bits, d.log_rows, glds, p.n_eff, x, y, xr, st, nparts);
-  // flip-flop records: this call's fields of d on the descriptor the kernel runs on
-  DevPass f = d;
-  const DevPass &k = p.fdesc;
-  f.quads = k.quads;
-  f.dtile = k.dtile;
-  f.nquads = k.nquads;
-  f.has_diag = k.has_diag;
-  f.dext_begin = k.dext_begin;
-  f.dext_end = k.dext_end;
-  memcpy(f.dbucket, k.dbucket, sizeof(f.dbucket));
-  memcpy(f.gbucket, k.gbucket, sizeof(f.gbucket));
-  memcpy(f.loop, k.loop, sizeof(f.loop));
-  return launch_tile_pass(f, f.tile_bits, f.log_rows, glds, p.n_eff, x, y, xr, st, nparts, &p.flip);
+// What one call adds to the description of a pass
+struct PassCall {
+  const void *zinit = nullptr, *zinit2 = nullptr;     // DevPass::zinit ... block_offset
+  double zscale = 0.0, z2re = 0.0, z2im = 0.0;
+  double *dot_out = nullptr;
+  uint32_t block_offset = 0;
+  unsigned nparts = 1;             // > 1: the 1 / nparts of the pass's workgroups that starts at block_offset
+};
+
+static int launch_pass(const dnm_mat *A, const PassOnDevice &p, const PassCall &c, const void *x, void *y,
+                       const void *xr, hipStream_t st) {
+  DevPass d = p.runs().desc;
+  d.zinit = c.zinit; d.zscale = c.zscale;
+  d.zinit2 = c.zinit2; d.z2re = c.z2re; d.z2im = c.z2im;
+  d.dot_out = c.dot_out;
+  d.block_offset = c.block_offset;
+  return launch_tile_pass(d, d.tile_bits, d.log_rows, (A->flags & DNM_MAT_USE_GLDS) != 0, p.n_eff, x, y, xr, st, c.nparts,
+                          p.reduced ? &p.reduced->flip : nullptr);
 }
 
 // partial sums a pass writes to dot_out: one per tile
 static size_t pass_dot_partials(const dnm_mat *, const PassOnDevice &p) {
-  return (size_t)1 << (p.n_eff - p.desc.tile_bits);
+  return (size_t)1 << (p.n_eff - p.whole.desc.tile_bits);
+}
+
+// the exports: pass lookup, and the checked copy-out of a host vector (item: the caller's size of one element; an empty
+// vector copies nothing and, unless `strict`, checks nothing)
+static int export_lookup(const dnm_mat *A, int remote, int idx, const PassOnDevice **p) {
+  DNM_CHECK(A, "null argument");
+  const auto &v = remote ? A->remote_passes : A->local_passes;
+  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
+  *p = v[idx].get();
+  return 0;
+}
+template <class T>
+static int export_copy(const std::vector<T> &v, void *out, size_t item, int64_t room, const char *type, const char *full,
+                       bool strict = false) {
+  if (!out || (v.empty() && !strict)) return 0;
+  DNM_CHECK(item == sizeof(T), "%s size mismatch (%zu vs %zu)", type, item, sizeof(T));
+  DNM_CHECK(room >= (int64_t)v.size(), "%s buffer too small", full);
+  if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(T));   // (an empty pass: no null source)
+  return 0;
+}
+// a description and its records (dnm_mat_export_pass, dnm_mat_export_flip_pass)
+static int export_records(const PassRecords &r, void *desc_out, size_t desc_bytes, void *quads_out, size_t quad_bytes,
+                          int max_quads, int *nquads, bool strict) {
+  *nquads = (int)r.quads.size();
+  if (desc_out) {
+    DNM_CHECK(desc_bytes == sizeof(DevPass), "DevPass size mismatch (%zu vs %zu)", desc_bytes, sizeof(DevPass));
+    memcpy(desc_out, &r.desc, sizeof(DevPass));
+  }
+  return export_copy(r.quads, quads_out, quad_bytes, max_quads, "DevQuad", "record", strict);
 }
 
 }  // namespace dnm
@@ -1249,6 +621,15 @@ static int setup_sc_block(dnm_mat *A) {
   return 0;
 }
 
+// the passes of one list of the plan, in their generic form
+static int build_passes(const dnm_mat &A, const std::vector<PassSpec> &specs, std::vector<std::unique_ptr<PassOnDevice>> *out) {
+  for (const PassSpec &ps : specs) {
+    out->emplace_back(new PassOnDevice());
+    DNM_TRY(build_pass(A, ps, out->back().get()));
+  }
+  return 0;
+}
+
 int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_offsets,
                    const int64_t *signs, const double *coeffs, const dnm_subspace *left,
                    const dnm_subspace *right, int xparity, int flags, const dnm_partition *part,
@@ -1504,20 +885,15 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
       A->plan.sends.clear();
     }
     if (A->plan.use_tiled) {
-      for (const PassSpec &ps : A->plan.local) {
-        std::unique_ptr<PassOnDevice> p(new PassOnDevice());
-        DNM_TRY(build_pass(*A, ps, p.get()));
-        A->local_passes.push_back(std::move(p));
-      }
-      for (const PassSpec &ps : A->plan.remote) {
-        std::unique_ptr<PassOnDevice> p(new PassOnDevice());
-        DNM_TRY(build_pass(*A, ps, p.get()));
-        A->remote_passes.push_back(std::move(p));
-      }
+      DNM_TRY(build_passes(*A, A->plan.local, &A->local_passes));
+      DNM_TRY(build_passes(*A, A->plan.remote, &A->remote_passes));
       // flip-flop records (plan.h: DevFlip): decided for the operator as a whole, from its passes as they stand
       decide_flip_bonds(A.get());
       for (size_t i = 0; i < A->plan.local.size(); ++i)
         DNM_TRY(build_flip_pass(*A, A->plan.local[i], A->local_passes[i].get()));
+      if (!A->host_only)
+        for (auto *v : {&A->local_passes, &A->remote_passes})
+          for (auto &p : *v) DNM_TRY(p->runs().upload());
     }
   }
   *out = A.release();
@@ -1734,15 +1110,13 @@ static int launch_sc(dnm_mat *A, int64_t win_start, int64_t win_len, const void 
                           win_start, dg, xw, y, nullptr, S(stream));
 }
 
-
-
 int dnm_mat_mult_local(dnm_mat *A, const void *x, void *y, void *stream) {
   DNM_CHECK(A && x && y, "null argument");
   DNM_CHECK(!A->host_only, "host-only handle cannot multiply");
   DNM_CHECK(x != y, "x and y must be different vectors");
   if (A->hypercube && A->plan.use_tiled) {
     for (auto &p : A->local_passes)
-      DNM_TRY(launch_pass(A, *p, p->desc, x, y, nullptr, S(stream)));
+      DNM_TRY(launch_pass(A, *p, PassCall(), x, y, nullptr, S(stream)));
     return 0;
   }
   DNM_CHECK(A->nranks == 1, "this subspace pair cannot run partitioned (use dnm_mat_mult_window)");
@@ -1760,11 +1134,12 @@ int dnm_mat_mult_local_part(dnm_mat *A, const void *x, void *y, int part, int np
   DNM_CHECK(A->hypercube && A->plan.use_tiled, "only the tiled hypercube passes run over a range of their workgroups");
   DNM_CHECK(nparts >= 1 && (nparts & (nparts - 1)) == 0 && part >= 0 && part < nparts, "bad range %d of %d", part, nparts);
   for (auto &p : A->local_passes) {
-    const unsigned grid = 1u << (p->n_eff - p->desc.tile_bits);
+    const unsigned grid = 1u << (p->n_eff - p->whole.desc.tile_bits);
     DNM_CHECK((unsigned)nparts <= grid, "more ranges than workgroups");
-    DevPass d = p->desc;
-    d.block_offset = (uint32_t)part * (grid / (unsigned)nparts);
-    DNM_TRY(launch_pass(A, *p, d, x, y, nullptr, S(stream), (unsigned)nparts));
+    PassCall c;
+    c.block_offset = (uint32_t)part * (grid / (unsigned)nparts);
+    c.nparts = (unsigned)nparts;
+    DNM_TRY(launch_pass(A, *p, c, x, y, nullptr, S(stream)));
   }
   return 0;
 }
@@ -1779,12 +1154,13 @@ int dnm_mat_local_part_bits(const dnm_mat *A, int *top_free_bit, int *gathers) {
   int top = -2;
   for (auto &p : A->local_passes) {
     uint64_t tb = 0;
-    for (int j = 0; j < p->desc.nseg; ++j) tb |= ((((uint64_t)1 << p->desc.seg_len[j]) - 1) << p->desc.seg_pos[j]);
+    const DevPass &d = p->whole.desc;
+    for (int j = 0; j < d.nseg; ++j) tb |= ((((uint64_t)1 << d.seg_len[j]) - 1) << d.seg_pos[j]);
     int hi = p->n_eff - 1;
     while (hi >= 0 && ((tb >> hi) & 1)) --hi;
     if (top == -2) top = hi; else if (top != hi) top = -1;
-    *gathers += (int)(p->desc.loop[LP_COUNT] - p->desc.loop[LP_GATHER_REAL]);     // gathered records
-    *gathers += (int)(p->desc.tab_loop[2] - p->desc.tab_loop[1]);
+    *gathers += (int)(d.loop[LP_COUNT] - d.loop[LP_GATHER_REAL]);     // gathered records
+    *gathers += (int)(d.tab_loop[2] - d.tab_loop[1]);
   }
   *top_free_bit = top < 0 ? -1 : top;
   return 0;
@@ -1856,19 +1232,19 @@ int dnm_mat_mult_lanczos(dnm_mat *A, const void *x, void *y, const void *z, doub
     DNM_TRY(dnm_mat_mult_local(A, x, y, stream));
     return vec_lanczos_dot_host(y, z, x, A->m_local, b, dot, S(stream));
   }
-  const bool fused_dot = A->local_passes.back()->desc.need_tile != 0;
+  const bool fused_dot = A->local_passes.back()->whole.desc.need_tile != 0;
   const size_t nblk = pass_dot_partials(A, *A->local_passes.back());
   double *part = nullptr;
   if (fused_dot) DNM_TRY(vec_scratch(((nblk + 1) * 3 + vk_reduce_scratch(3)) * sizeof(double), &part));
   for (size_t i = 0; i < A->local_passes.size(); ++i) {
-    DevPass d = A->local_passes[i]->desc;
+    PassCall c;
     if (i == 0 && z) {
-      DNM_CHECK(!d.accumulate, "internal: first pass accumulates");
-      d.zinit = z;
-      d.zscale = b;
+      DNM_CHECK(!A->local_passes[i]->whole.desc.accumulate, "internal: first pass accumulates");
+      c.zinit = z;
+      c.zscale = b;
     }
-    if (fused_dot && i + 1 == A->local_passes.size()) d.dot_out = part;
-    DNM_TRY(launch_pass(A, *A->local_passes[i], d, x, y, nullptr, S(stream)));
+    if (fused_dot && i + 1 == A->local_passes.size()) c.dot_out = part;
+    DNM_TRY(launch_pass(A, *A->local_passes[i], c, x, y, nullptr, S(stream)));
   }
   if (!fused_dot) return vec_lanczos_dot_host(y, nullptr, x, A->m_local, 0.0, dot, S(stream));
   DNM_TRY(vk_reduce_partials(part, (int)nblk, 3, part + 3 * nblk, S(stream), part + 3 * nblk + 3));
@@ -1896,16 +1272,16 @@ int dnm_mat_mult_sub2(dnm_mat *A, const void *x, void *y, const void *z, double 
   DNM_CHECK(!A->host_only, "host-only handle cannot multiply");
   if (A->hypercube && A->plan.use_tiled && !A->local_passes.empty()) {
     for (size_t i = 0; i < A->local_passes.size(); ++i) {
-      DevPass d = A->local_passes[i]->desc;
+      PassCall c;
       if (i == 0) {
-        DNM_CHECK(!d.accumulate, "internal: first pass accumulates");
-        d.zinit = z;
-        d.zscale = b;
-        d.zinit2 = z2;
-        d.z2re = c_re;
-        d.z2im = c_im;
+        DNM_CHECK(!A->local_passes[i]->whole.desc.accumulate, "internal: first pass accumulates");
+        c.zinit = z;
+        c.zscale = b;
+        c.zinit2 = z2;
+        c.z2re = c_re;
+        c.z2im = c_im;
       }
-      DNM_TRY(launch_pass(A, *A->local_passes[i], d, x, y, nullptr, S(stream)));
+      DNM_TRY(launch_pass(A, *A->local_passes[i], c, x, y, nullptr, S(stream)));
     }
     return 0;
   }
@@ -2179,7 +1555,7 @@ int dnm_mat_mult_remote(dnm_mat *A, int32_t recv_index, const void *x_recv, void
   DNM_CHECK(recv_index >= 0 && recv_index < (int)A->remote_passes.size(), "rank %d has no receive %d", A->rank,
             recv_index);
   const auto &p = A->remote_passes[recv_index];
-  return launch_pass(A, *p, p->desc, x_recv, (char *)y + (size_t)p->y_off * 16, x_recv, S(stream));
+  return launch_pass(A, *p, PassCall(), x_recv, (char *)y + (size_t)p->y_off * 16, x_recv, S(stream));
 }
 
 int dnm_mat_norm_inf(dnm_mat *A, double *nrm, void *stream) {
@@ -2244,8 +1620,8 @@ int dnm_mat_plan_describe(const dnm_mat *A, char *buf, size_t buflen) {
   if (A->hypercube && A->plan.use_tiled) {
     // masks of many terms run as table records (plan.h: DevTab); said only when there are any: the plans without keep their text
     size_t ntab = 0, nquad = 0;
-    for (const auto &p : A->local_passes) { ntab += p->h_tabs.size(); nquad += p->desc.loop[LP_COUNT] - p->desc.loop[0]; }
-    for (const auto &p : A->remote_passes) { ntab += p->h_tabs.size(); nquad += p->desc.loop[LP_COUNT] - p->desc.loop[0]; }
+    for (const auto &p : A->local_passes) { ntab += p->whole.tabs.size(); nquad += p->whole.desc.loop[LP_COUNT] - p->whole.desc.loop[0]; }
+    for (const auto &p : A->remote_passes) { ntab += p->whole.tabs.size(); nquad += p->whole.desc.loop[LP_COUNT] - p->whole.desc.loop[0]; }
     if (ntab) s += "table records: " + std::to_string(ntab) + " (beside " + std::to_string(nquad) + " records of four terms)\n";
     // (flip-flop records -- plan.h: DevFlip -- add no line: tests pin the line count of the chain plans; dnm_mat_export_flip)
   }
@@ -2255,99 +1631,54 @@ int dnm_mat_plan_describe(const dnm_mat *A, char *buf, size_t buflen) {
 
 int dnm_mat_export_pass(const dnm_mat *A, int remote, int idx, void *desc_out, size_t desc_bytes,
                         void *quads_out, size_t quad_bytes, int max_quads, int *nquads) {
-  DNM_CHECK(A && nquads, "null argument");
-  const auto &v = remote ? A->remote_passes : A->local_passes;
-  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
-  const PassOnDevice &p = *v[idx];
-  *nquads = (int)p.h_quads.size();
-  if (desc_out) {
-    DNM_CHECK(desc_bytes == sizeof(DevPass), "DevPass size mismatch (%zu vs %zu)", desc_bytes, sizeof(DevPass));
-    memcpy(desc_out, &p.desc, sizeof(DevPass));
-  }
-  if (quads_out) {
-    DNM_CHECK(quad_bytes == sizeof(DevQuad), "DevQuad size mismatch (%zu vs %zu)", quad_bytes, sizeof(DevQuad));
-    DNM_CHECK(max_quads >= *nquads, "record buffer too small");
-    if (!p.h_quads.empty()) memcpy(quads_out, p.h_quads.data(), p.h_quads.size() * sizeof(DevQuad));   // (an empty pass: no null source)
-  }
-  return 0;
+  const PassOnDevice *p;
+  DNM_CHECK(nquads, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  return export_records(p->whole, desc_out, desc_bytes, quads_out, quad_bytes, max_quads, nquads, true);
 }
 
 int dnm_mat_export_tabs(const dnm_mat *A, int remote, int idx, void *tabs_out, size_t tab_bytes, int max_tabs, int *ntabs,
                         double *vals_out, int64_t max_vals, int64_t *nvals) {
-  DNM_CHECK(A && ntabs && nvals, "null argument");
-  const auto &v = remote ? A->remote_passes : A->local_passes;
-  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
-  const PassOnDevice &p = *v[idx];
-  *ntabs = (int)p.h_tabs.size();
-  *nvals = (int64_t)p.h_tabvals.size();
-  if (tabs_out && !p.h_tabs.empty()) {
-    DNM_CHECK(tab_bytes == sizeof(DevTab), "DevTab size mismatch (%zu vs %zu)", tab_bytes, sizeof(DevTab));
-    DNM_CHECK(max_tabs >= *ntabs, "record buffer too small");
-    memcpy(tabs_out, p.h_tabs.data(), p.h_tabs.size() * sizeof(DevTab));
-  }
-  if (vals_out && !p.h_tabvals.empty()) {
-    DNM_CHECK(max_vals >= *nvals, "table buffer too small");
-    memcpy(vals_out, p.h_tabvals.data(), p.h_tabvals.size() * sizeof(double));
-  }
-  return 0;
+  const PassOnDevice *p;
+  DNM_CHECK(ntabs && nvals, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  *ntabs = (int)p->whole.tabs.size();
+  *nvals = (int64_t)p->whole.tabvals.size();
+  DNM_TRY(export_copy(p->whole.tabs, tabs_out, tab_bytes, max_tabs, "DevTab", "record"));
+  return export_copy(p->whole.tabvals, vals_out, sizeof(double), max_vals, "double", "table");
 }
 
 int dnm_mat_export_dtile(const dnm_mat *A, int remote, int idx, double *out, int64_t n) {
-  DNM_CHECK(A && out, "null argument");
-  const auto &v = remote ? A->remote_passes : A->local_passes;
-  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
-  const PassOnDevice &p = *v[idx];
-  DNM_CHECK((int64_t)p.h_dtile.size() == n, "the pass has %zu tabulated diagonal entries, not %lld", p.h_dtile.size(),
-            (long long)n);
-  memcpy(out, p.h_dtile.data(), p.h_dtile.size() * sizeof(double));
-  return 0;
+  const PassOnDevice *p;
+  DNM_CHECK(out, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  DNM_CHECK((int64_t)p->whole.dtile.size() == n, "the pass has %zu tabulated diagonal entries, not %lld",
+            p->whole.dtile.size(), (long long)n);
+  return export_copy(p->whole.dtile, out, sizeof(double), n, "double", "table");
 }
 
 int dnm_mat_export_flip(const dnm_mat *A, int remote, int idx, void *flips_out, size_t flip_bytes, int max_flips,
                         int *nflips, uint32_t *loops_out, double *dconst) {
-  DNM_CHECK(A && nflips, "null argument");
-  const auto &v = remote ? A->remote_passes : A->local_passes;
-  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
-  const PassOnDevice &p = *v[idx];
-  if (p.h_flips.empty()) {      // the pass runs on its generic records
-    *nflips = -1;
-    return 0;
-  }
-  *nflips = (int)p.flip.loop[FL_COUNT];
-  if (loops_out) memcpy(loops_out, p.flip.loop, sizeof(p.flip.loop));
-  if (dconst) *dconst = p.flip.dconst;
-  if (flips_out && *nflips > 0) {
-    DNM_CHECK(flip_bytes == sizeof(DevFlip), "DevFlip size mismatch (%zu vs %zu)", flip_bytes, sizeof(DevFlip));
-    DNM_CHECK(max_flips >= *nflips, "record buffer too small");
-    memcpy(flips_out, p.h_flips.data(), (size_t)*nflips * sizeof(DevFlip));
-  }
-  return 0;
+  const PassOnDevice *p;
+  DNM_CHECK(nflips, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  *nflips = p->reduced ? (int)p->reduced->flips.size() : -1;      // -1: the pass runs on its generic records
+  if (!p->reduced) return 0;
+  if (loops_out) memcpy(loops_out, p->reduced->flip.loop, sizeof(p->reduced->flip.loop));
+  if (dconst) *dconst = p->reduced->flip.dconst;
+  return export_copy(p->reduced->flips, flips_out, flip_bytes, max_flips, "DevFlip", "record");
 }
 
 int dnm_mat_export_flip_pass(const dnm_mat *A, int remote, int idx, void *desc_out, size_t desc_bytes, void *quads_out,
                              size_t quad_bytes, int max_quads, int *nquads, double *dtile_out, int64_t max_dtile,
                              int64_t *ndtile) {
-  DNM_CHECK(A && nquads && ndtile, "null argument");
-  const auto &v = remote ? A->remote_passes : A->local_passes;
-  DNM_CHECK(idx >= 0 && idx < (int)v.size(), "pass index out of range");
-  const PassOnDevice &p = *v[idx];
-  DNM_CHECK(!p.h_flips.empty(), "the pass has no flip-flop form");
-  *nquads = (int)p.h_fquads.size();
-  *ndtile = (int64_t)p.h_fdtile.size();
-  if (desc_out) {
-    DNM_CHECK(desc_bytes == sizeof(DevPass), "DevPass size mismatch (%zu vs %zu)", desc_bytes, sizeof(DevPass));
-    memcpy(desc_out, &p.fdesc, sizeof(DevPass));
-  }
-  if (quads_out && !p.h_fquads.empty()) {
-    DNM_CHECK(quad_bytes == sizeof(DevQuad), "DevQuad size mismatch (%zu vs %zu)", quad_bytes, sizeof(DevQuad));
-    DNM_CHECK(max_quads >= *nquads, "record buffer too small");
-    memcpy(quads_out, p.h_fquads.data(), p.h_fquads.size() * sizeof(DevQuad));
-  }
-  if (dtile_out && !p.h_fdtile.empty()) {
-    DNM_CHECK(max_dtile >= *ndtile, "table buffer too small");
-    memcpy(dtile_out, p.h_fdtile.data(), p.h_fdtile.size() * sizeof(double));
-  }
-  return 0;
+  const PassOnDevice *p;
+  DNM_CHECK(nquads && ndtile, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  DNM_CHECK(p->reduced, "the pass has no flip-flop form");
+  *ndtile = (int64_t)p->reduced->dtile.size();
+  DNM_TRY(export_records(*p->reduced, desc_out, desc_bytes, quads_out, quad_bytes, max_quads, nquads, false));
+  return export_copy(p->reduced->dtile, dtile_out, sizeof(double), max_dtile, "double", "table");
 }
 
 int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_passes, int *tiled,

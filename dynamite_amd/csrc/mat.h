@@ -34,30 +34,32 @@ struct SubOwned {
   int init(const dnm_subspace *s, bool want_device);
 };
 
-struct PassOnDevice {
-  DevPass desc{};
-  std::vector<DevQuad> h_quads;   // host copy (diagnostics / host-only handles)
-  DevBuf quads;
-  std::vector<double> h_dtile;    // in-tile diagonal per tile coordinate (DevPass::dtile), host copy
-  DevBuf dtile;
-  std::vector<DevTab> h_tabs;     // table records (plan.h: DevTab) and their tables, host copies
-  std::vector<double> h_tabvals;
-  DevBuf tabs, tabvals;
-  // passes with flip-flop records (plan.h: DevFlip): what the kernel runs on -- the flip-flop records, and fdesc with the
-  // remaining generic records (h_fquads) and the reduced diagonal (h_fdtile); desc / h_quads / h_dtile above keep
-  // describing the whole pass generically
-  std::vector<DevFlip> h_flips;
+// What one launch of the tiled kernel reads, as passes.cpp builds it on the host
+struct PassRecords {
+  DevPass desc{};                 // geometry and record ranges; its device pointers are null until upload()
+  std::vector<DevQuad> quads;
+  std::vector<double> dtile;      // in-tile diagonal per tile coordinate (DevPass::dtile)
+  std::vector<DevTab> tabs;       // table records (plan.h: DevTab) and their tables
+  std::vector<double> tabvals;
+  bool is_reduced = false;        // the flip-flop form of a pass (plan.h: DevFlip): flips / flip belong to it
+  std::vector<DevFlip> flips;
   DevFlipPass flip{};
-  DevPass fdesc{};
-  std::vector<DevQuad> h_fquads;
-  std::vector<double> h_fdtile;
-  DevBuf flips, fquads, fdtile;
+  DevBuf d_quads, d_dtile, d_tabs, d_tabvals, d_flips;
+  int upload();                   // the only place that writes a device pointer into desc / flip
+};
+
+struct PassOnDevice {
+  PassRecords whole;                      // the pass in the generic vocabulary (dnm_mat_export_pass)
+  // passes with flip-flop records: those, the generic records that remain and the diagonal the exchanges leave
+  std::unique_ptr<PassRecords> reduced;
+  PassRecords &runs() { return reduced ? *reduced : whole; }      // what the kernel is launched on
+  const PassRecords &runs() const { return reduced ? *reduced : whole; }
   int partner = -1;
   int n_eff = 0;                  // index bits the pass sweeps
   int64_t y_off = 0, src_off = 0; // partner passes: first local row / first partner amplitude
 };
 
-// A mask as a flip-flop record (plan.h: DevFlip; flip_classify / decide_flip_bonds in mat.cpp)
+// A mask as a flip-flop record (plan.h: DevFlip; flip_classify / decide_flip_bonds in passes.cpp)
 struct FlipBond {
   bool ok = false;        // the mask runs as a flip-flop record
   bool exch = false;      // ... as a tile record, an exchange: the diagonal carries what it leaves

@@ -119,3 +119,35 @@ def test_flipflop_bonds_without_zz(monkeypatch, name, L, B, logR, mode, amin):
             print(name, L, B, logR, "flipflop", knob, "flags", flags, "records", n, "err %.3e tol %.3e" % (err, tol_for(arrs, x)))
             assert err <= tol_for(arrs, x), mat.describe()
             mat.destroy()
+
+
+@pytest.mark.parametrize("name", ["mbl", "aniso"])
+def test_flipflop_ranges_of_one_pass(monkeypatch, name):
+    """dnm_mat_mult_local_part on a pass with flip-flop records: four ranges of the workgroups of the one local pass
+    (L = 14, one tile of 2^10, everything else gathered: 13 records in all four classes, 7 / 2 / 3 / 1 in the order of
+    the FL_* ranges -- the smallest chain that has all four) write, bit for bit, what the whole launch writes -- same kernel, same arithmetic per row, only the grid and the first workgroup
+    differ -- and leave no row out."""
+    L = 14
+    cfg(monkeypatch, 10, 2, 1, 3)
+    H, arrs, sub, x, ref = _case(name, L)
+    for knob in ("1", "0"):
+        monkeypatch.setenv("DNM_FLIPFLOP", knob)
+        for flags in (0, _lib.MAT_USE_GLDS):
+            mat = shell(H, sub, flags=flags)
+            vals = [C.c_int() for _ in range(6)]
+            _lib.check(_lib.lib().dnm_mat_plan_counts(mat.handle, *[C.byref(v) for v in vals]))
+            assert vals[0].value == 1 and vals[2].value == 1, mat.describe()
+            assert _classes(mat) == (13 if knob == "1" else 0), mat.describe()
+            xv = vec_from(x, mat.swz_right)
+            yw, yp = backend.Vec(mat.M, swz=mat.swz_left), backend.Vec(mat.M, swz=mat.swz_left)
+            yw.set_local_from_numpy(np.full(1 << L, np.nan + 1j * np.nan))
+            yp.set_local_from_numpy(np.full(1 << L, np.nan + 1j * np.nan))
+            _lib.check(_lib.lib().dnm_mat_mult_local(mat.handle, xv.ptr, yw.ptr, None))
+            for part in range(4):
+                _lib.check(_lib.lib().dnm_mat_mult_local_part(mat.handle, xv.ptr, yp.ptr, part, 4, None))
+            y_whole, y_parts = yw.local_numpy(), yp.local_numpy()
+            assert np.array_equal(y_parts, y_whole), mat.describe()
+            err = np.max(np.abs(y_whole - ref))
+            print(name, "flipflop", knob, "flags", flags, "err %.3e tol %.3e" % (err, tol_for(arrs, x)))
+            assert err <= tol_for(arrs, x), mat.describe()
+            mat.destroy()

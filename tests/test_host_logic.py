@@ -644,7 +644,7 @@ def test_pass_addressing_fits_32_bit_offsets(L, P, S, flags_amin):
     thread's part of the tile coordinate can reach -- the low B - LOGR tile bits and what the layout folds them onto --
     lies in DevPass::pos_tmask, below bit 28, for every pass of the plans the benchmark configurations take (a tile
     that reaches higher, like the layout-B operator of the transposed exchange at 2^31 amplitudes per rank, gets
-    more rows per thread: csrc/mat.cpp build_pass)."""
+    more rows per thread: csrc/passes.cpp build_pass)."""
     from dynamite_amd import models, msc_tools, _lib
     from dynamite_amd.subspaces import Full
     from plan_emulator import HostMat, vec_pos
@@ -700,7 +700,7 @@ def test_complement_ranges():
                                         ("localized", 13, "full"), ("ising", 14, "full"), ("ising", 15, "parity0"),
                                         ("ising", 15, "parity1"), ("xsum", 13, "full")])
 def test_real_packed_operator_form(monkeypatch, name, L, sub):
-    """DNM_MAT_REAL_PACKED (csrc/mat.cpp pack_opform): the records of a real-symmetric operator in real arithmetic --
+    """DNM_MAT_REAL_PACKED (csrc/passes.cpp pack_opform): the records of a real-symmetric operator in real arithmetic --
     vectors of dim / 2 elements holding two real amplitudes each -- run through the kernel emulation reproduce the
     oracle's y = H x for a real x; an operator with an imaginary matrix element has no such form."""
     from dynamite_amd import models, msc_tools, _lib
