@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdynamite_amd.so")
-SOURCES = ["matvec_kernels.hip", "row_fused_kernels.hip", "sc3_kernels.hip", "sc3g_kernels.hip", "vec_kernels.hip", "rdm_kernels.hip", "rdm_sector_kernels.hip", "plan.cpp", "sc3_perm.cpp", "passes.cpp", "mat.cpp", "vec_api.cpp", "krylov.cpp", "comm.cpp"]
+SOURCES = ["matvec_kernels.hip", "row_fused_kernels.hip", "sc3_kernels.hip", "sc3g_kernels.hip", "vec_kernels.hip", "rdm_kernels.hip", "rdm_sector_kernels.hip", "plan.cpp", "sc3_perm.cpp", "passes.cpp", "mat.cpp", "vec_api.cpp", "krylov_host.cpp", "krylov.cpp", "comm.cpp"]
 ARCH = "gfx950"
 # tile_pass_kernel sits at the 128-VGPR edge of 4 waves per SIMD; these two scheduler options of the AMDGPU backend
 # measured -2.1 % on the L=30 multiply, same box (profiles/r02_exp22_sched.txt; max-ilp / iterative-minreg: +12...17 %);
@@ -52,7 +52,8 @@ def sanitizer_runtime():
 def build_sanitized(force=False, verbose=False):
     """ASan + UBSan build of the HOST side of the library (CPU only, never for the GPU box): every source compiled
     with the sanitizers on its host side (`-Xarch_host`) -- planner, operator handles, the SpinConserve layout tables, the
-    exchange schedules, the Krylov drivers and the kernels' host-side launch wrappers -- and linked into
+    exchange schedules, the Krylov drivers (their host arithmetic, csrc/krylov_host.cpp, is also checked on its own by a
+    plain C++ program, tests/test_krylov_host.py) and the kernels' host-side launch wrappers -- and linked into
     libdynamite_amd_san.so.  Host-only handles (DNM_MAT_HOST_ONLY) never launch, so the CPU tests run on it unchanged:
     `DNM_LIB_VARIANT=san LD_PRELOAD=<sanitizer_runtime()> python -m pytest ...` (tools/sanitize.sh)."""
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(os.path.dirname(HERE), "include", "dynamite_amd.h")]

@@ -1,6 +1,8 @@
 """Interior eigenpairs (eigsolve(target=, interior='filter')): what runs without a GPU -- the filter's parameters
 (dnm_interior_filter_plan) against their closed forms, the factorised recurrence of csrc/krylov.cpp
-(Ops::apply_fold) restated in numpy on a matrix of known spectrum, and the argument checks of the Python entry."""
+(Ops::apply_fold, its coefficients and final scale in FoldPoly, csrc/krylov_host.h) restated in numpy on a matrix of
+known spectrum, and the argument checks of the Python entry.  (The window estimate and the dense helpers:
+tests/test_krylov_host.py.)"""
 import ctypes as C
 
 import numpy as np
