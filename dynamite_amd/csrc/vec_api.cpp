@@ -65,6 +65,17 @@ int vec_lanczos_update_host(void *p, const void *v, const void *u, int64_t n, do
 using namespace dnm;
 static hipStream_t S(void *s) { return (hipStream_t)s; }
 
+// vec_pos(i, sw) folds index bits [sw, 2 sw - 4) onto bits [4, sw): it maps [0, n) onto itself when no such bit is
+// ever set (n <= 2^sw) or when the bits below sw run through all their values under each (n a multiple of 2^sw)
+static int swizzle_fits(int64_t n, int sw) {
+  DNM_CHECK(sw == 0 || (sw >= 5 && sw <= 24), "swizzle shift %d out of range", sw);
+  const int64_t run = (int64_t)1 << sw;
+  DNM_CHECK(sw == 0 || n <= run || n % run == 0,
+            "a vector of %lld elements has no layout of swizzle shift %d: beyond 2^%d elements the size must be a "
+            "multiple of 2^%d", (long long)n, sw, sw, sw);
+  return 0;
+}
+
 extern "C" {
 
 int dnm_vec_set(void *x, int64_t n, double re, double im, void *stream) {
@@ -106,21 +117,21 @@ int dnm_vec_norm2(const void *x, int64_t n, double *out, void *stream) {
 
 int dnm_vec_set_random_swz(void *x, int64_t n, uint64_t seed, int64_t offset, int swizzle, void *stream) {
   DNM_CHECK(x || n == 0, "null vector");
-  DNM_CHECK(swizzle == 0 || (swizzle >= 5 && swizzle <= 24), "swizzle shift %d out of range", swizzle);
+  DNM_TRY(swizzle_fits(n, swizzle));
   return vk_random(x, n, seed, offset, S(stream), swizzle);
 }
 
 int dnm_vec_unpack_real(void *dst, const void *src, int64_t n_packed, int swizzle_packed, int swizzle_out, void *stream) {
   DNM_CHECK(dst && src && dst != src && n_packed >= 0, "bad vector");
-  for (int sw : {swizzle_packed, swizzle_out})
-    DNM_CHECK(sw == 0 || (sw >= 5 && sw <= 24), "swizzle shift %d out of range", sw);
+  DNM_TRY(swizzle_fits(n_packed, swizzle_packed));
+  DNM_TRY(swizzle_fits(2 * n_packed, swizzle_out));
   return vk_unpack_real(dst, src, n_packed, swizzle_packed, swizzle_out, S(stream));
 }
 
 int dnm_vec_swizzle_copy(void *dst, const void *src, int64_t n, int swizzle, void *stream) {
   DNM_CHECK((dst && src) || n == 0, "null vector");
   DNM_CHECK(dst != src, "dnm_vec_swizzle_copy works out of place");
-  DNM_CHECK(swizzle == 0 || (swizzle >= 5 && swizzle <= 24), "swizzle shift %d out of range", swizzle);
+  DNM_TRY(swizzle_fits(n, swizzle));
   return vk_swizzle_copy(dst, src, n, swizzle, S(stream));
 }
 

@@ -361,6 +361,10 @@ int dnm_vec_norm2(const void *x, int64_t n, double *out, void *stream);         
  * (seed, global index = offset + i): distribution of State.set_random
  * (states.py:292-316), not its MT19937 stream. */
 int dnm_vec_set_random(void *x, int64_t n, uint64_t seed, int64_t offset, void *stream);
+/* Size condition of the three calls below that take a swizzle shift S != 0: the swizzle maps [0, n) onto itself only
+ * when n <= 2^S (no folded bit is ever set: the layout is index order) or n is a multiple of 2^S.  Any other n is
+ * refused before anything is launched (n = 2^S + 16 would send element 2^S to position n).  dnm_vec_unpack_real
+ * holds n_packed to it under swizzle_packed and 2 * n_packed under swizzle_out. */
 /* the same stream of numbers for a vector in the swizzled layout (element i gets what index order would give it) */
 int dnm_vec_set_random_swz(void *x, int64_t n, uint64_t seed, int64_t offset, int swizzle, void *stream);
 /* dst[i] = src[i ^ sw(i)]: swizzled <-> index order (the map is an involution); dst != src */
