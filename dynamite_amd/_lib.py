@@ -71,7 +71,8 @@ class DevPass(C.Structure):
                 ("tile_bits", C.c_int32), ("log_rows", C.c_int32),
                 ("swz_shift", C.c_int32), ("swz_xor_y", C.c_uint32), ("swz_xor_src", C.c_uint32), ("block_offset", C.c_uint32),
                 ("pos_tmask", C.c_uint32), ("dtile", vp), ("tabs", vp), ("tabvals", vp), ("tab_loop", C.c_uint32 * 3),
-                ("pad_tab", C.c_uint32), ("gbucket", C.c_uint32 * (MAXR + 1)), ("pad_g", C.c_uint32)]
+                ("pad_tab", C.c_uint32), ("gbucket", C.c_uint32 * (MAXR + 1)), ("pad_g", C.c_uint32),
+                ("dblock", vp), ("dsel_n", C.c_uint32), ("pad_d", C.c_uint32), ("dsel_mask", C.c_uint64 * 3)]
 
 
 class DevTab(C.Structure):
@@ -167,6 +168,8 @@ SIGNATURES = {
                                       C.POINTER(C.c_uint32), f64p]),
     "dnm_mat_export_flip_pass": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_int,
                                            C.POINTER(C.c_int), f64p, C.c_int64, i64p]),
+    "dnm_mat_export_diag_tables": (C.c_int, [vp, C.c_int, C.c_int, f64p, C.c_int64, i64p, f64p, C.c_int64, i64p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "dnm_mat_ownership": (C.c_int, [vp, i64p, i64p]),
     "dnm_mat_column_window": (C.c_int, [vp, i64p, i64p, vp]),
     "dnm_mat_column_chunks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), C.c_int64, vp]),

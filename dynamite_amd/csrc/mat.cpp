@@ -149,7 +149,8 @@ static int upload_to(DevBuf &buf, const std::vector<T> &v, const T **dev) {
 }
 int PassRecords::upload() {
   DNM_TRY(upload_to(d_quads, quads, &desc.quads));
-  if (!dtile.empty()) DNM_TRY(upload_to(d_dtile, dtile, &desc.dtile));
+  if (!dtile.empty()) DNM_TRY(upload_to(d_dtile, dblock.empty() ? dtile : dtile_sections(), &desc.dtile));
+  if (!dblock.empty()) DNM_TRY(upload_to(d_dblock, dblock, &desc.dblock));
   if (!tabs.empty()) DNM_TRY(upload_to(d_tabs, tabs, &desc.tabs));
   if (!tabs.empty()) DNM_TRY(upload_to(d_tabvals, tabvals, &desc.tabvals));
   // (a pass that only carries the reduced diagonal has no flip-flop record: the kernel still takes a non-null pointer)
@@ -208,7 +209,13 @@ static int export_records(const PassRecords &r, void *desc_out, size_t desc_byte
   *nquads = (int)r.quads.size();
   if (desc_out) {
     DNM_CHECK(desc_bytes == sizeof(DevPass), "DevPass size mismatch (%zu vs %zu)", desc_bytes, sizeof(DevPass));
-    memcpy(desc_out, &r.desc, sizeof(DevPass));
+    // (the fields of the diagonal's tables are derived data with an export of their own, dnm_mat_export_diag_tables:
+    // the description handed out here is the same with and without them)
+    DevPass d = r.desc;
+    d.dblock = nullptr;
+    d.dsel_n = 0;
+    memset(d.dsel_mask, 0, sizeof(d.dsel_mask));
+    memcpy(desc_out, &d, sizeof(DevPass));
   }
   return export_copy(r.quads, quads_out, quad_bytes, max_quads, "DevQuad", "record", strict);
 }
@@ -891,6 +898,9 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
       decide_flip_bonds(A.get());
       for (size_t i = 0; i < A->plan.local.size(); ++i)
         DNM_TRY(build_flip_pass(*A, A->plan.local[i], A->local_passes[i].get()));
+      // the diagonal of what the kernel runs on as tables (DevPass::dblock), where it qualifies
+      for (auto *v : {&A->local_passes, &A->remote_passes})
+        for (auto &p : *v) DNM_TRY(build_diag_tables(*A, p.get()));
       if (!A->host_only)
         for (auto *v : {&A->local_passes, &A->remote_passes})
           for (auto &p : *v) DNM_TRY(p->runs().upload());
@@ -1587,7 +1597,15 @@ int dnm_mat_set_norm(dnm_mat *A, double nrm) {
 int dnm_mat_plan_describe(const dnm_mat *A, char *buf, size_t buflen) {
   DNM_CHECK(A && buf && buflen, "null argument");
   std::string s;
-  if (A->hypercube) s = A->plan.describe(A->op);
+  if (A->hypercube) {
+    // a pass whose diagonal the kernel reads from tables (DevPass::dblock) says so at the end of its own line; the
+    // others keep their text
+    std::vector<std::string> notes[2];
+    const std::vector<std::unique_ptr<PassOnDevice>> *lists[2] = {&A->local_passes, &A->remote_passes};
+    for (int k = 0; k < 2; ++k)
+      for (const auto &p : *lists[k]) notes[k].push_back(p->runs().dblock.empty() ? "" : " diag_tables=1");
+    s = A->plan.describe(A->op, &notes[0], &notes[1]);
+  }
   else if (A->use_sc3) {
     const Sc3Tab &T = A->sc3->ly->host;
     char tmp[512];
@@ -1679,6 +1697,23 @@ int dnm_mat_export_flip_pass(const dnm_mat *A, int remote, int idx, void *desc_o
   *ndtile = (int64_t)p->reduced->dtile.size();
   DNM_TRY(export_records(*p->reduced, desc_out, desc_bytes, quads_out, quad_bytes, max_quads, nquads, false));
   return export_copy(p->reduced->dtile, dtile_out, sizeof(double), max_dtile, "double", "table");
+}
+
+int dnm_mat_export_diag_tables(const dnm_mat *A, int remote, int idx, double *dblock_out, int64_t max_dblock,
+                               int64_t *ndblock, double *dtile_out, int64_t max_dtile, int64_t *ndtile,
+                               uint64_t *masks_out, int *nmasks) {
+  const PassOnDevice *p;
+  DNM_CHECK(ndblock && ndtile && nmasks, "null argument");
+  DNM_TRY(export_lookup(A, remote, idx, &p));
+  const PassRecords &r = p->runs();
+  const bool have = !r.dblock.empty();
+  *ndblock = (int64_t)r.dblock.size();
+  *ndtile = have ? (int64_t)r.dtile_sections().size() : 0;
+  *nmasks = have ? (int)r.desc.dsel_n : 0;
+  if (!have) return 0;
+  if (masks_out) memcpy(masks_out, r.desc.dsel_mask, sizeof(r.desc.dsel_mask));
+  DNM_TRY(export_copy(r.dblock, dblock_out, sizeof(double), max_dblock, "double", "table"));
+  return export_copy(r.dtile_sections(), dtile_out, sizeof(double), max_dtile, "double", "table");
 }
 
 int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_passes, int *tiled,

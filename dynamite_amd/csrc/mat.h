@@ -44,7 +44,11 @@ struct PassRecords {
   bool is_reduced = false;        // the flip-flop form of a pass (plan.h: DevFlip): flips / flip belong to it
   std::vector<DevFlip> flips;
   DevFlipPass flip{};
-  DevBuf d_quads, d_dtile, d_tabs, d_tabvals, d_flips;
+  // the rest of the diagonal as tables (DevPass::dblock; build_diag_tables), derived from quads / dtile / flip.dconst:
+  // dblock empty: the pass has none; dsect: the sectioned in-tile table (empty with dblock set: one section, dtile itself)
+  std::vector<double> dblock, dsect;
+  const std::vector<double> &dtile_sections() const { return dsect.empty() ? dtile : dsect; }
+  DevBuf d_quads, d_dtile, d_tabs, d_tabvals, d_flips, d_dblock;
   int upload();                   // the only place that writes a device pointer into desc / flip
 };
 

@@ -469,7 +469,9 @@ constexpr int tile_waves_per_simd(int B, int LOGR, bool TAB = false) {
 // parameter leaves as it was)
 // FLIP: the instance that also knows flip-flop records (plan.h: DevFlip, FP: their ranges and the constant of the
 // diagonal); passes without any run on the instances without, which this parameter leaves as they were
-template <int B, int LOGR, bool GLDS, int GV, bool PACK, bool TAB, bool FLIP>
+// DT: the instance for passes whose diagonal is all tables (DevPass::dblock, chosen by the launch): it has none of the
+// list code, and the instances without it are what they were
+template <int B, int LOGR, bool GLDS, int GV, bool PACK, bool TAB, bool FLIP, bool DT>
 __device__ __forceinline__ void tile_pass_body(const DevPass &P, const c128 *__restrict__ x, c128 *__restrict__ y,
                                                const c128 *__restrict__ xr, const DevFlipPass &FP) {
   constexpr int R = 1 << LOGR;
@@ -596,8 +598,18 @@ __device__ __forceinline__ void tile_pass_body(const DevPass &P, const c128 *__r
   // ---- diagonal, part 1 (before the barrier, under the tile loads): the terms
   // whose sign mask lies outside the tile are the same for the whole workgroup.
   // Each lane evaluates one term, a butterfly sums them across the wavefront.
+  // The diagonal from tables (DevPass::dblock, the DT instances): part 1 is one number per workgroup, read by ONE scalar
+  // load -- here, before the barrier, so that no LDS read ever shares the counter with it (see flip_tile) --, and the
+  // parities of sbase over the up to three selector masks (scalar unit) pick the section of the per-coordinate table
+  // that part 2 reads
+  static_assert(!DT || (!TAB && !PACK), "no table-driven diagonal on the TAB and PACK instances");
   double dext = 0.0;
-  if (P.has_diag) {
+  uint32_t dsec = 0;
+  if constexpr (DT) {
+    dext = ((const __attribute__((address_space(4))) double *)P.dblock)[blockIdx.x + P.block_offset];
+#pragma unroll
+    for (int i = 0; i < MAXDSEL; ++i) dsec |= ((uint32_t)__popcll(sbase & P.dsel_mask[i]) & 1u) << i;
+  } else if (P.has_diag) {
     const uint32_t lane = tid & 63u;
     const uint32_t nterm = (P.dext_end - P.dext_begin) * 4u;
     for (uint32_t t0 = 0; t0 < nterm; t0 += 64u) {
@@ -644,7 +656,17 @@ __device__ __forceinline__ void tile_pass_body(const DevPass &P, const c128 *__r
   // thread's k bits; a length-R Walsh-Hadamard butterfly then yields all R row
   // values at once.  (Reads only the thread's own amplitudes of the tile.)
   auto diag_part2 = [&]() {
-  if (P.has_diag) {
+  if constexpr (DT) {
+    // everything tabulated: D(row) = the workgroup's number + the section's entry at the row's tile coordinate
+    const double *__restrict__ dsect = P.dtile + ((size_t)dsec << B) + tid;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const double Dk = dext + dsect[k * NT];
+      c128 xs = tile[tid + k * NT];
+      ar[k] = fma(Dk, xs.x, ar[k]);
+      ai[k] = fma(Dk, xs.y, ai[k]);
+    }
+  } else if (P.has_diag) {
     double D[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) D[j] = 0.0;
@@ -789,19 +811,19 @@ __device__ __forceinline__ void tile_pass_body(const DevPass &P, const c128 *__r
   }
 }
 
-template <int B, int LOGR, bool GLDS, int GV, bool PACK = false, bool TAB = false>
+template <int B, int LOGR, bool GLDS, int GV, bool PACK = false, bool TAB = false, bool DT = false>
 __global__ void __launch_bounds__(1 << (B - LOGR), tile_waves_per_simd(B, LOGR, TAB))
 tile_pass_kernel(const DevPass P, const c128 *__restrict__ x, c128 *__restrict__ y,
                  const c128 *__restrict__ xr) {
-  tile_pass_body<B, LOGR, GLDS, GV, PACK, TAB, false>(P, x, y, xr, DevFlipPass{});
+  tile_pass_body<B, LOGR, GLDS, GV, PACK, TAB, false, DT>(P, x, y, xr, DevFlipPass{});
 }
 
 // passes with flip-flop records (early gathers; no table records, no real-packed form)
-template <int B, int LOGR, bool GLDS>
+template <int B, int LOGR, bool GLDS, bool DT = false>
 __global__ void __launch_bounds__(1 << (B - LOGR), tile_waves_per_simd(B, LOGR, false))
 tile_pass_flip_kernel(const DevPass P, const DevFlipPass FP, const c128 *__restrict__ x, c128 *__restrict__ y,
                       const c128 *__restrict__ xr) {
-  tile_pass_body<B, LOGR, GLDS, 1, false, false, true>(P, x, y, xr, FP);
+  tile_pass_body<B, LOGR, GLDS, 1, false, false, true, DT>(P, x, y, xr, FP);
 }
 
 #ifdef DNM_PHASE_TIMING
@@ -833,14 +855,20 @@ static int launch_cfg(const DevPass &P, bool glds, int n_loc, const void *x, voi
   const bool pack = (P.cache_policy & 256) != 0;          // real-packed records: their own instance (early gathers only)
   // table records / grouped diagonal terms: their own instance (early gathers, plain tile loads)
   const bool tab = P.tab_loop[2] > 0 || P.gbucket[MAXR] > P.gbucket[0];
+  // the diagonal as tables (DevPass::dblock): the instances without the list code (build_diag_tables gives the tables
+  // to passes with early gathers, without table records, not real-packed)
+  const bool dt = P.has_diag && P.dblock != nullptr;
+  DNM_CHECK(!dt || (!pack && !tab && gv == 1), "internal: a table-driven diagonal in a pass that cannot run it");
   if (F) {      // flip-flop records: their own instances (build_pass gives them to passes with early gathers only)
     DNM_CHECK(!pack && !tab && gv == 1, "internal: flip-flop records in a pass that cannot run them");
     using fkern_t = void (*)(const DevPass, const DevFlipPass, const c128 *, c128 *, const c128 *);
-    fkern_t fk = glds ? tile_pass_flip_kernel<B, LOGR, true> : tile_pass_flip_kernel<B, LOGR, false>;
-    static size_t fattr_done[2] = {0, 0};
-    if (fattr_done[glds ? 1 : 0] < lds) {
+    fkern_t fk = dt ? (glds ? tile_pass_flip_kernel<B, LOGR, true, true> : tile_pass_flip_kernel<B, LOGR, false, true>)
+                    : (glds ? tile_pass_flip_kernel<B, LOGR, true> : tile_pass_flip_kernel<B, LOGR, false>);
+    static size_t fattr_done[4] = {0, 0, 0, 0};
+    const int fslot = (glds ? 1 : 0) + (dt ? 2 : 0);
+    if (fattr_done[fslot] < lds) {
       DNM_HIP(hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      fattr_done[glds ? 1 : 0] = lds;
+      fattr_done[fslot] = lds;
     }
     hipLaunchKernelGGL(fk, dim3(grid), dim3(NT), lds, st, P, *F, (const c128 *)x, (c128 *)y, (const c128 *)xr);
     DNM_HIP(hipGetLastError());
@@ -848,11 +876,12 @@ static int launch_cfg(const DevPass &P, bool glds, int n_loc, const void *x, voi
   }
   if (pack) k = tile_pass_kernel<B, LOGR, false, 1, true>;
   else if (tab) k = tile_pass_kernel<B, LOGR, false, 1, false, true>;
+  else if (dt) k = glds ? tile_pass_kernel<B, LOGR, true, 1, false, false, true> : tile_pass_kernel<B, LOGR, false, 1, false, false, true>;
   else if (glds) k = tile_pass_kernel<B, LOGR, true, 1>;
   else if (gv == 0) k = tile_pass_kernel<B, LOGR, false, 0>;
   else k = tile_pass_kernel<B, LOGR, false, 1>;
-  static size_t attr_done[6] = {0, 0, 0, 0, 0, 0};
-  const int slot = pack ? 4 : (tab ? 5 : (glds ? 3 : gv));
+  static size_t attr_done[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int slot = pack ? 4 : (tab ? 5 : (dt ? (glds ? 7 : 6) : (glds ? 3 : gv)));
   if (attr_done[slot] < lds) {
     DNM_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_done[slot] = lds;

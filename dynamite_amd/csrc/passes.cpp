@@ -646,4 +646,63 @@ int build_flip_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out) {
   return 0;
 }
 
+// The diagonal of a pass as tables (plan.h: DevPass::dblock), derived from the records the kernel would read otherwise --
+// the dext list, the bucket lists, the in-tile table and the constant of the flip-flop form -- once the pass has its final
+// form (after build_flip_pass).  Built where the in-tile table is, the pass has neither grouped diagonal terms nor table
+// records (those run on the kernel instance that keeps the lists), its gathers are early, the terms of the bucket lists have at most MAXDSEL
+// distinct outside parts and the pass no more than 2^MAXDBLOCK_BITS workgroups; DNM_DIAG_BLOCK_TABLE=0: never.  Changes
+// nothing that dnm_mat_export_pass / _dtile / _flip_pass hand out.
+int build_diag_tables(const dnm_mat &A, PassOnDevice *out) {
+  PassRecords &r = out->runs();
+  DevPass &d = r.desc;
+  const char *e = knob("DNM_DIAG_BLOCK_TABLE");
+  // (the kernel instances that read the tables: early gathers, not real-packed)
+  if (!d.has_diag || (e && e[0] == '0') || r.dtile.empty() || A.op.packed || !(d.cache_policy & 32)) return 0;
+  if (!r.tabs.empty() || d.gbucket[MAXR] > d.gbucket[0]) return 0;
+  const int B = d.tile_bits, R = 1 << d.log_rows, nbb = d.n_eff - B;
+  if (nbb < 0 || nbb > MAXDBLOCK_BITS) return 0;
+  // the distinct outside parts of the terms that see the tile and bits outside it
+  std::vector<uint64_t> sel;
+  for (uint32_t q = d.dbucket[0]; q < d.dbucket[R]; ++q)
+    for (uint32_t j = 0; j < r.quads[q].nslots; ++j) {
+      const uint64_t m = r.quads[q].sign_ext[j];
+      if (m && std::find(sel.begin(), sel.end(), m) == sel.end()) sel.push_back(m);
+    }
+  if ((int)sel.size() > MAXDSEL) return 0;
+  // per workgroup: the terms outside the tile at sign_base | deposit(b), as the kernel forms the block part of a row
+  r.dblock.resize((size_t)1 << nbb);
+  for (uint32_t b = 0; b < ((uint32_t)1 << nbb); ++b) {
+    uint64_t base = 0;
+    for (int j = 0; j < d.nbseg; ++j)
+      base |= (uint64_t)((b >> d.bseg_off[j]) & ((1u << d.bseg_len[j]) - 1u)) << d.bseg_pos[j];
+    const uint64_t sbase = d.sign_base | base;
+    double v = r.is_reduced ? r.flip.dconst : 0.0;
+    for (uint32_t q = d.dext_begin; q < d.dext_end; ++q)
+      for (uint32_t j = 0; j < r.quads[q].nslots; ++j)
+        v += parity64(sbase & r.quads[q].sign_ext[j]) ? -r.quads[q].coeff[j] : r.quads[q].coeff[j];
+    r.dblock[b] = v;
+  }
+  // per tile coordinate: one section per combination of the outside parities
+  d.dsel_n = (uint32_t)sel.size();
+  for (size_t i = 0; i < sel.size(); ++i) d.dsel_mask[i] = sel[i];
+  if (!sel.empty()) {
+    const size_t T = (size_t)1 << B;
+    r.dsect.resize(T << sel.size());
+    for (size_t s = 0; s < ((size_t)1 << sel.size()); ++s) {
+      double *sec = r.dsect.data() + s * T;
+      std::copy(r.dtile.begin(), r.dtile.end(), sec);
+      for (uint32_t q = d.dbucket[0]; q < d.dbucket[R]; ++q)
+        for (uint32_t j = 0; j < r.quads[q].nslots; ++j) {
+          const DevQuad &Q = r.quads[q];
+          uint32_t po = 0;      // the parity of the term's outside part in this section
+          for (size_t i = 0; i < sel.size(); ++i)
+            if (sel[i] == Q.sign_ext[j]) po = (uint32_t)(s >> i) & 1u;
+          for (uint32_t tc = 0; tc < (uint32_t)T; ++tc)
+            sec[tc] += ((__builtin_popcount(tc & Q.sign_tile[j]) ^ po) & 1) ? -Q.coeff[j] : Q.coeff[j];
+        }
+    }
+  }
+  return 0;
+}
+
 }  // namespace dnm

@@ -11,5 +11,6 @@ int pack_opform(OpForm *op);
 int build_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out);
 void decide_flip_bonds(dnm_mat *A);      // after every build_pass of the handle
 int build_flip_pass(const dnm_mat &A, const PassSpec &ps, PassOnDevice *out);
+int build_diag_tables(const dnm_mat &A, PassOnDevice *out);      // last: on the form of the pass that the kernel runs on
 
 }  // namespace dnm

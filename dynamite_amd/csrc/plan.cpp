@@ -364,12 +364,13 @@ int make_plan(const OpForm &op, int rank, int nranks, const PlanConfig &cfg_in, 
   return 0;
 }
 
-std::string Plan::describe(const OpForm &op) const {
+std::string Plan::describe(const OpForm &op, const std::vector<std::string> *local_notes,
+                           const std::vector<std::string> *remote_notes) const {
   std::ostringstream os;
   os << "n=" << n << " n_loc=" << n_loc << " rank=" << rank << "/" << nranks
      << " tiled=" << (use_tiled ? 1 : 0) << " B=" << cfg.B << " logR=" << cfg.logR
      << " mode=" << cfg.mode << " masks=" << op.masks.size() << "\n";
-  auto dump = [&](const char *kind, const PassSpec &ps, size_t i) {
+  auto dump = [&](const char *kind, const PassSpec &ps, size_t i, const std::vector<std::string> *notes) {
     os << kind << " pass " << i << ":";
     if (ps.B != cfg.B || (ps.logR && ps.logR != cfg.logR)) os << " B=" << ps.B << " logR=" << (ps.logR ? ps.logR : cfg.logR);
     os << " segs";
@@ -381,10 +382,11 @@ std::string Plan::describe(const OpForm &op) const {
     if (ps.partner >= 0)
       os << " partner=" << ps.partner << " rows [" << ps.y_off << ",+2^" << ps.n_eff << ") from partner offset "
          << ps.src_off;
+    if (notes && i < notes->size()) os << (*notes)[i];
     os << "\n";
   };
-  for (size_t i = 0; i < local.size(); ++i) dump("local", local[i], i);
-  for (size_t i = 0; i < remote.size(); ++i) dump("remote", remote[i], i);
+  for (size_t i = 0; i < local.size(); ++i) dump("local", local[i], i, local_notes);
+  for (size_t i = 0; i < remote.size(); ++i) dump("remote", remote[i], i, remote_notes);
   return os.str();
 }
 

@@ -178,8 +178,23 @@ struct DevPass {
   // the groups are listed by the k part of their sign mask: bucket j = [gbucket[j], gbucket[j + 1]).
   uint32_t gbucket[MAXR + 1];
   uint32_t pad_g;
+  // The rest of the diagonal as tables (passes.cpp: build_diag_tables), for passes whose diagonal has no grouped terms
+  // and at most MAXDSEL distinct outside parts among the terms that see the tile AND bits outside it.  Nothing of a
+  // diagonal depends on x, so all of it is fixed when the handle is built:
+  //   dblock[b]: the sum of the terms outside the tile (the dext list) for workgroup b of the pass -- block_offset
+  //     included --, with DevFlipPass::dconst added in: one scalar load per workgroup;
+  //   dtile then holds 2^dsel_n SECTIONS of 2^B doubles: section s = the in-tile terms plus every term of the bucket
+  //     lists, each with the sign its outside part takes when parity(sbase & dsel_mask[i]) = bit i of s.
+  // The kernel reads D(row) = dblock[b] + dtile[(s << B) + tile coordinate]; the dext and dbucket lists stay in the
+  // description (dnm_mat_export_pass) but are not read.  Null: the lists are evaluated as before.
+  const double *dblock;
+  uint32_t dsel_n;
+  uint32_t pad_d;
+  uint64_t dsel_mask[3];
 };
 constexpr uint32_t MAXDGROUPS = 64;
+constexpr int MAXDSEL = 3;                  // DevPass::dsel_mask
+constexpr int MAXDBLOCK_BITS = 22;          // cap of DevPass::dblock: 2^22 workgroups, 32 MB (production plans: 2^18 - 2^19)
 
 // ---- flip-flop records ---------------------------------------------------------
 // A mask that flips two bits with real terms whose row coefficient is c where the two bits DIFFER and 0 where they agree
@@ -274,7 +289,10 @@ struct Plan {
   struct Send { int partner; int64_t offset, count; };
   std::vector<Send> sends;
   bool use_tiled = false;                      // false: generic row-gather kernel only
-  std::string describe(const OpForm &op) const;
+  // one line for the plan and one per pass; local_notes / remote_notes (optional, one entry per pass of the list): text that
+  // ends the pass's line -- what the record builder has to say about a pass (mat.cpp: " diag_tables=1")
+  std::string describe(const OpForm &op, const std::vector<std::string> *local_notes = nullptr,
+                       const std::vector<std::string> *remote_notes = nullptr) const;
 };
 
 PlanConfig plan_config_from_env();

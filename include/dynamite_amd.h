@@ -247,6 +247,14 @@ int dnm_mat_export_flip(const dnm_mat *A, int remote, int idx, void *flips_out, 
 int dnm_mat_export_flip_pass(const dnm_mat *A, int remote, int idx, void *desc_out, size_t desc_bytes, void *quads_out,
                              size_t quad_bytes, int max_quads, int *nquads, double *dtile_out, int64_t max_dtile,
                              int64_t *ndtile);
+/* the diagonal of a pass as tables, of the form of the pass that the kernel runs on (plan.h: DevPass::dblock): one double
+ * per workgroup (the terms outside the tile, the constant of a flip-flop form included), 2^nmasks sections of 2^tile_bits
+ * doubles (section s: the terms that see the tile, those that also see outside bits with the sign their outside part takes
+ * when parity(row & masks[i]) = bit i of s) and the up to three masks; *ndblock = 0 for a pass that evaluates its
+ * diagonal from the records; null buffers: the counts alone */
+int dnm_mat_export_diag_tables(const dnm_mat *A, int remote, int idx, double *dblock_out, int64_t max_dblock,
+                               int64_t *ndblock, double *dtile_out, int64_t max_dtile, int64_t *ndtile,
+                               uint64_t *masks_out, int *nmasks);
 
 /* --- partitioned multiply: replaces the VecScatterCreateToAll all-gather of
  * bcuda_template_2.cu:161-171 with an XOR-partner exchange. ---------------- */
