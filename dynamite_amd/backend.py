@@ -1526,6 +1526,31 @@ def create_mat(masks, mask_offsets, signs, coeffs, left_c, right_c, xparity=Fals
     return h
 
 
+def export_sc3(handle, name):
+    """One host table of a SpinConserve handle's passes as bytes (dnm_mat_export_sc3; ``name``: see dynamite_amd.h)."""
+    n = C.c_size_t()
+    _lib.check(_lib.lib().dnm_mat_export_sc3(handle, name.encode(), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.check(_lib.lib().dnm_mat_export_sc3(handle, name.encode(), buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+SC3_TABLES = ("rowsel", "needT", "hops", "wnb", "ptab", "pcoef", "permA", "permB", "bond", "dlo", "dt_sign", "dt_coef",
+              "dt_group")
+
+
+def sc3_op_fields(handle):
+    """The "op" record of dnm_mat_export_sc3 as a dict."""
+    raw = export_sc3(handle, "op")
+    u = np.frombuffer(raw[:24], dtype=np.uint64)
+    v = np.frombuffer(raw[24:], dtype=np.int32)
+    names = ["ndt", "ngroups"] + [None] * 4 + ["nldsA", "ngatA", "nldsB", "ngatB", "nhp"] + [None] * 18 + \
+            ["tiled", "graph", "sym", "real", "diag_mode"]
+    out = {"present": int(u[0]), "bondsA": int(u[1]), "bondsB": int(u[2]), "glo": v[2:6].tolist(), "ptab_row": v[11:29].tolist()}
+    out.update({k: int(x) for k, x in zip(names, v.tolist()) if k})
+    return out
+
+
 def _relabelled(masks, lc, rc, xparity, site_perm):
     """The descriptors a SpinConserve pair in the internal layout is built on: with a site relabelling
     (dnm_subspace.site_perm) when the operator's bond graph gains from one -- ``site_perm``: None = choose

@@ -224,60 +224,6 @@ static int export_records(const PassRecords &r, void *desc_out, size_t desc_byte
 
 using namespace dnm;
 
-namespace dnm {
-std::vector<ScMask> sc_masks(const std::vector<int64_t> &masks, const std::vector<int64_t> &mask_offsets,
-                             const std::vector<int64_t> &signs, const std::vector<double> &rcoef, int L, bool xparity) {
-  std::vector<ScMask> scm(masks.size());
-  for (size_t mi = 0; mi < masks.size(); ++mi) {
-    ScMask &e = scm[mi];
-    memset(&e, 0, sizeof(e));
-    const uint64_t mask = (uint64_t)masks[mi];
-    e.dead = __builtin_popcountll(mask) & 1;
-    if (xparity && L >= 3 && __builtin_popcountll(mask) == L - 2 && !((mask >> (L - 1)) & 1ull)) {
-      // a hop between spin i and spin L-1 times the global flip (XParity.reduce_msc): every spin but those two
-      const uint64_t miss = ~mask & ((((uint64_t)1 << (L - 1)) - 1));
-      const int i = __builtin_ctzll(miss);
-      const uint64_t pairbits = ((uint64_t)1 << i) | ((uint64_t)1 << (L - 1));
-      bool local = true;
-      for (int64_t t = mask_offsets[mi]; t < mask_offsets[mi + 1]; ++t)
-        if ((uint64_t)signs[t] & ~pairbits) local = false;
-      if (!local) continue;
-      e.pair = 2;
-      e.lo = i;
-      e.hi = L - 1;
-      for (int64_t t = mask_offsets[mi]; t < mask_offsets[mi + 1]; ++t) {
-        // the column state keeps spin i down and spin L-1 up; the sign masks do not meet the mask: a real element
-        const double c = (((uint64_t)signs[t] >> i) & 1) ? -rcoef[t] : rcoef[t];
-        e.up_re += c;
-        e.dn_re += c;
-      }
-      continue;
-    }
-    if (__builtin_popcountll(mask) != 2) continue;
-    const int lo = __builtin_ctzll(mask), hi = 63 - __builtin_clzll(mask);
-    bool local = true;
-    for (int64_t t = mask_offsets[mi]; t < mask_offsets[mi + 1]; ++t)
-      if ((uint64_t)signs[t] & ~mask) local = false;
-    if (!local) continue;
-    e.pair = 1;
-    e.fast = hi == lo + 1;
-    e.lo = lo;
-    e.hi = hi;
-    for (int64_t t = mask_offsets[mi]; t < mask_offsets[mi + 1]; ++t) {
-      const uint64_t sg = (uint64_t)signs[t];
-      const double rc = rcoef[t];
-      const bool imag = parity64(mask & sg);
-      // column state (bra) carries the moved spin: bit hi for an up hop, bit lo for a down hop
-      const double up = ((sg >> hi) & 1) ? -rc : rc;
-      const double dn = ((sg >> lo) & 1) ? -rc : rc;
-      (imag ? e.up_im : e.up_re) += up;
-      (imag ? e.dn_im : e.dn_re) += dn;
-    }
-  }
-  return scm;
-}
-}  // namespace dnm
-
 extern "C" {
 
 const char *dnm_last_error(void) { return g_err.c_str(); }
@@ -1714,6 +1660,48 @@ int dnm_mat_export_diag_tables(const dnm_mat *A, int remote, int idx, double *db
   if (masks_out) memcpy(masks_out, r.desc.dsel_mask, sizeof(r.desc.dsel_mask));
   DNM_TRY(export_copy(r.dblock, dblock_out, sizeof(double), max_dblock, "double", "table"));
   return export_copy(r.dtile_sections(), dtile_out, sizeof(double), max_dtile, "double", "table");
+}
+
+// One table of the SpinConserve passes as its builder left it on the host (sc3_tables.cpp), by name: rowsel needT hops
+// wnb ptab pcoef permA permB bond dlo dt_sign dt_coef dt_group, the bytes the device gets; "op": what the kernels are
+// handed beside the tables (include/dynamite_amd.h has the order).  Null out: the size alone.
+int dnm_mat_export_sc3(const dnm_mat *A, const char *name, void *out, size_t max_bytes, size_t *nbytes) {
+  DNM_CHECK(A && name && nbytes, "null argument");
+  DNM_CHECK(A->use_sc3 && A->sc3, "the operator does not run on the SpinConserve layout's passes");
+  const Sc3Mat &M = *A->sc3;
+  const std::string n = name;
+  const void *src = nullptr;
+  size_t len = 0;
+  std::vector<unsigned char> packed;
+#define DNM_SC3_TABLE(NAME_)                                        \
+  if (n == #NAME_) {                                                \
+    src = M.NAME_.data();                                           \
+    len = M.NAME_.size() * sizeof(M.NAME_[0]);                      \
+  } else
+  DNM_SC3_TABLE(rowsel) DNM_SC3_TABLE(needT) DNM_SC3_TABLE(hops) DNM_SC3_TABLE(wnb) DNM_SC3_TABLE(ptab)
+  DNM_SC3_TABLE(pcoef) DNM_SC3_TABLE(permA) DNM_SC3_TABLE(permB) DNM_SC3_TABLE(bond) DNM_SC3_TABLE(dlo)
+  DNM_SC3_TABLE(dt_sign) DNM_SC3_TABLE(dt_coef) DNM_SC3_TABLE(dt_group)
+#undef DNM_SC3_TABLE
+  if (n == "op") {
+    const Sc3Op &O = M.op;
+    const uint64_t u[3] = {O.present, O.bondsA, O.bondsB};
+    std::vector<int32_t> v = {O.ndt, O.ngroups, (int32_t)O.glo[0], (int32_t)O.glo[1], (int32_t)O.glo[2], (int32_t)O.glo[3],
+                              O.nldsA, O.ngatA, O.nldsB, O.ngatB, O.nhp};
+    v.insert(v.end(), O.ptab_row, O.ptab_row + SC3_MAXA + 2);
+    for (int f : {(int)M.tiled, (int)M.graph, (int)M.sym, (int)M.real, M.diag_mode}) v.push_back(f);
+    packed.resize(sizeof u + v.size() * sizeof(int32_t));
+    memcpy(packed.data(), u, sizeof u);
+    memcpy(packed.data() + sizeof u, v.data(), v.size() * sizeof(int32_t));
+    src = packed.data();
+    len = packed.size();
+  } else {
+    DNM_CHECK(false, "no table '%s' of the SpinConserve passes", name);
+  }
+  *nbytes = len;
+  if (!out) return 0;
+  DNM_CHECK(max_bytes >= len, "table '%s' has %zu bytes, the buffer %zu", name, len, max_bytes);
+  if (len) memcpy(out, src, len);
+  return 0;
 }
 
 int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_passes, int *tiled,

@@ -5,25 +5,13 @@
 #include <memory>
 #include <vector>
 
+#include "dev_buf.h"
 #include "kernels.h"
 #include "plan.h"
 #include "sc3.h"
 #include "subspace.h"
 
 namespace dnm {
-
-// Device allocation that frees itself.
-struct DevBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  int alloc(size_t nbytes);
-  int upload(const void *host, size_t nbytes);
-  void release();
-};
 
 // A subspace with owned host tables and their device mirrors.
 struct SubOwned {

@@ -16,6 +16,12 @@
 //               bonds inside W from LDS, the W/T boundary and the bonds inside T gathered at uniform offsets.
 // Nothing like this exists in the reference (a PETSc Vec is opaque there as well); the maps to and from the
 // reference order are dnm_vec_layout_copy / dnm_vec_layout_positions.
+//
+// Who does what: sc3_tables.cpp builds every table of the layout and of an operator's two passes on the host, as members
+// of Sc3Layout / Sc3Mat, and calls no HIP function (tests/sc3_tables_check.cpp links it alone); Sc3Layout::upload and
+// Sc3Mat::upload are the only places that write a device pointer into the structs the kernels are handed (Sc3Tab, Sc3Op);
+// sc3_kernels.hip / sc3g_kernels.hip hold the kernels, sc3_launch.h the one launcher of both families, sc3_shape.h the
+// thread counts and tile sizes that the tables and the launches must agree on.
 #pragma once
 
 #include <array>
@@ -25,6 +31,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dev_buf.h"
 #include "kernels.h"
 
 namespace dnm {
@@ -115,7 +122,6 @@ struct Sc3Layout {
   // the complex kernel run on these tables (rows of pitch / 2 elements).
   Sc3Tab host_h{}, dev_h{};
   std::vector<int64_t> ibase_h, icoff_h;
-  void *d_ibase_h = nullptr, *d_icoff_h = nullptr;
   int64_t dim = 0;                 // C(L, k)
   bool on_device = false;
   std::vector<int64_t> ibase, nbase, icoff, ncoff, nck;
@@ -127,17 +133,22 @@ struct Sc3Layout {
   std::vector<uint32_t> tidx;      // [1 << t] place of a T block in tseq (0xffffffff: empty block)
   std::vector<size_t> rowstart;    // [tseq.size() + 1] first row of a block inside `rows`
   std::vector<uint64_t> w_nb;
-  void *d_w_nb = nullptr;
   std::vector<uint16_t> lo_rlo, lo_rhi;
-  void *d_lo_rlo = nullptr, *d_lo_rhi = nullptr;
-  void *d_ibase = nullptr, *d_nbase = nullptr, *d_icoff = nullptr, *d_ncoff = nullptr, *d_lo_pat = nullptr,
-       *d_w_pat = nullptr, *d_lo_rank = nullptr, *d_w_rank = nullptr, *d_cbin = nullptr, *d_rows = nullptr, *d_nck = nullptr;
+  DevBuf d_ibase, d_nbase, d_icoff, d_ncoff, d_lo_pat, d_w_pat, d_lo_rank, d_w_rank, d_cbin, d_rows, d_nck, d_w_nb,
+      d_lo_rlo, d_lo_rhi, d_ibase_h, d_icoff_h;
   Sc3Layout() = default;
   Sc3Layout(const Sc3Layout &) = delete;
   Sc3Layout &operator=(const Sc3Layout &) = delete;
-  ~Sc3Layout();
-  // 0 on success; want_device: upload the tables
+  // 0 on success: the host tables (host, host_h), then upload() if want_device
   int init(int L, int k, int a, int w, bool want_device, int order = 0);
+  int upload();                    // the only place that writes a device pointer into dev / dev_h
+ private:
+  void build_patterns();           // cbin, nck, lo_pat / lo_rank, w_pat / w_rank, rs
+  void build_window_partners();    // w_nb
+  int build_split_rank();          // lo_rlo, lo_rhi
+  int build_offsets();             // icoff, ncoff, the block sequence with ibase, nbase, rows
+  void point_tables();             // host and host_h at the vectors
+ public:
   // is T one of the blocks [b0, b1) of the block sequence?
   bool in_range(uint32_t T, uint32_t b0, uint32_t b1) const {
     return T < tidx.size() && tidx[T] != 0xffffffffu && tidx[T] >= b0 && tidx[T] < b1;
@@ -148,6 +159,13 @@ struct Sc3Layout {
 bool sc3_valid(int L, int k, int a, int w);
 // shared, cached layouts (a process uses a handful): the pointer stays valid for the life of the process
 const Sc3Layout *sc3_get(int L, int k, int a, int w, bool want_device, int order = 0);
+
+// the rows of the blocks [T0, T1) of the sequence inside Ly.rows and the offsets of that range; what the vector-level
+// operations below ask of a range: a reference side (ref_side), no partition of a relabelled layout (perm_whole)
+struct RowRange { size_t first, count; int64_t ioff, noff; };
+RowRange row_range(const Sc3Layout &Ly, uint32_t T0, uint32_t T1);
+int ref_side(const Sc3Layout &Ly, const RowRange &r);
+int perm_whole(const Sc3Layout &Ly, const Sc3Perm *perm, const RowRange &r);
 
 // ---- vector-level operations (sc3_kernels.hip) --------------------------------------------------------------
 // All of them act on the part of a vector that covers the blocks [T0, T1) OF THE LAYOUT'S BLOCK SEQUENCE (Sc3Layout::tseq;
@@ -243,7 +261,6 @@ struct Sc3Mat {
   uint32_t T0 = 0, T1 = 0;         // the blocks of the layout's sequence this rank's rows cover
   int64_t row0 = 0;                // internal position of its first row
   std::vector<uint32_t> rowsel;    // its rows (T << w | W), for the row kernel
-  void *d_rowsel = nullptr;
   std::vector<char> needT;         // T blocks its rows read (own blocks included)
   bool tiled = false;              // two tiled passes (every off-diagonal mask is a pair hop); else the row kernel
   bool graph = false;              // ... of sc3g_kernels.hip (any bond graph); false: the chain kernels
@@ -252,20 +269,39 @@ struct Sc3Mat {
   bool real = false;               // real vectors (DNM_MAT_REAL_PACKED): sc3_lo_pass_r, window pass on the halved tables
   int diag_mode = 0;               // 0: no diagonal terms; 2: on the fly; 1: needs the cached diagonal
   Sc3Op op{};
-  std::vector<uint32_t> permA, permB;
-  void *d_permA = nullptr, *d_permB = nullptr, *d_bond = nullptr, *d_dlo = nullptr, *d_dt_sign = nullptr,
-       *d_dt_coef = nullptr, *d_dt_group = nullptr, *d_hops = nullptr, *d_wnb = nullptr, *d_ptab = nullptr, *d_pcoef = nullptr;
+  std::vector<uint32_t> permA, permB;   // dispatch orders of the lo pass (8 entries per workgroup) and the window pass
   std::vector<Sc3Hop> hops;        // ldsA, gatA, ldsB, gatB back to back
   std::vector<uint8_t> wnb;
   std::vector<uint16_t> ptab;
   std::vector<double> pcoef;
+  std::vector<double> bond;        // Sc3Op::bond
+  std::vector<double> dlo, dt_coef;     // Sc3Op::dlo, dt_sign, dt_coef, dt_group (whatever diag_mode ends as)
+  std::vector<uint64_t> dt_sign;
+  std::vector<int32_t> dt_group;
+  DevBuf d_rowsel, d_permA, d_permB, d_bond, d_dlo, d_dt_sign, d_dt_coef, d_dt_group, d_hops, d_wnb, d_ptab, d_pcoef;
   Sc3Mat() = default;
   Sc3Mat(const Sc3Mat &) = delete;
   Sc3Mat &operator=(const Sc3Mat &) = delete;
-  ~Sc3Mat();
+  // the operator (in the layout's labelling; scm: sc_masks of it) on the blocks [T0, T1) of the layout's sequence: the
+  // host tables by the steps below, then upload() if want_device
   int init(const Sc3Layout *layout, const std::vector<int64_t> &masks, const std::vector<int64_t> &mask_offsets,
            const std::vector<int64_t> &signs, const std::vector<double> &rcoef, const std::vector<ScMask> &scm,
            bool want_device, uint32_t T0, uint32_t T1, bool real_vectors = false);
+  int upload();                    // the only place that writes a device pointer into op
+ private:
+  // the steps of init, in its order; each fills host members and nothing else (sc3_tables.cpp)
+  void need_blocks(const std::vector<int64_t> &masks);                                    // rowsel, needT
+  void classify(const std::vector<int64_t> &masks, const std::vector<ScMask> &scm);       // tiled, graph
+  void chain_bonds(const std::vector<int64_t> &masks, const std::vector<ScMask> &scm);    // sym, bond, op.present / bondsA / bondsB
+  bool graph_hops(const std::vector<int64_t> &masks, const std::vector<ScMask> &scm);     // hops, wnb, op.n*; false: too many
+  void lo_partner_table();                                                                // ptab, pcoef, op.nhp / ptab_row
+  void split_diagonal(const std::vector<int64_t> &masks, const std::vector<int64_t> &mask_offsets,
+                      const std::vector<int64_t> &signs, const std::vector<double> &rcoef);    // diag_mode, dlo, dt_*, op.glo
+  std::vector<std::vector<uint32_t>> own_blocks_by_popcount() const;
+  std::vector<std::vector<uint32_t>> lo_groups_pairs() const, lo_groups_graph() const;   // rows that share an XCD
+  void lo_dispatch();                                                                     // permA
+  int window_dispatch();                                                                  // permB
+ public:
   // the internal positions [lo, hi] this rank's rows read; marks the chunks of 2^shift positions among them
   void window(int64_t *lo, int64_t *hi) const;
   void chunks(int shift, int64_t first_chunk, int64_t nchunks, uint8_t *map) const;

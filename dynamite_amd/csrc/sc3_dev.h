@@ -3,6 +3,7 @@
 #pragma once
 
 #include "sc3.h"
+#include "sc3_shape.h"
 
 namespace dnm {
 
@@ -54,13 +55,6 @@ __device__ __forceinline__ double flip(double c, uint32_t parity_bit) {
 #endif
 
 constexpr int ilog2c(int v) { return v <= 1 ? 0 : 1 + ilog2c(v >> 1); }
-constexpr uint32_t SC3_NOROW = 1u << 29;       // lo pass: a sub-group slot without a row
-
-constexpr int cbinom(int n, int k) {
-  long long r = 1;
-  for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i;
-  return (int)r;
-}
 
 // row (T, W) of a workgroup: everything the kernels derive from the perm entry
 struct RowId {
@@ -82,9 +76,6 @@ __device__ __forceinline__ RowId decode_row(uint32_t e, const Sc3Tab &S) {
   return r;
 }
 
-// entries of the lo pass's LDS tile: what the workgroup's threads hold (RPT entries each), at least the longest row
-constexpr int sc3_lo_cap(int a, int nt) { return ((cbinom(a, a / 2) + nt - 1) / nt) * nt; }
-
 // waves per SIMD a tiled pass can have: what its LDS tile lets be resident (two workgroups per CU for the 64 KB
 // tiles), at most 8 -- the register budget follows from it (128 registers at 512 threads, 64 at 1024)
 constexpr int sc3_win_waves(int nt, int tile_kb) {
@@ -94,18 +85,6 @@ constexpr int sc3_win_waves(int nt, int tile_kb) {
   const int w = wgs * nt / 256;
   return w > 8 ? 8 : (w < 1 ? 1 : w);
 }
-
-// shape of the real lo pass: NTR threads with PPT pairs each (DNM_SC3R_SHAPE 0: as many threads as the complex pass and
-// twice its entries per thread -- 1024 x 8 entries, a 64 KB tile, two workgroups per CU; 1: half the threads, 512 x 8, a
-// 32 KB tile, four workgroups per CU; 2: 1024 x 4, 32 KB, two per CU)
-#ifndef DNM_SC3R_SHAPE
-#define DNM_SC3R_SHAPE 0
-#endif
-constexpr int sc3r_threads(int nt) { return (DNM_SC3R_SHAPE == 1 && nt >= 512) ? nt / 2 : nt; }
-constexpr int sc3r_pairs(int a, int nt) {
-  return (DNM_SC3R_SHAPE == 2 && nt >= 512) ? (cbinom(a, a / 2) / 2 + nt - 1) / nt : (cbinom(a, a / 2) + nt - 1) / nt;
-}
-constexpr int sc3_lo_cap_r(int a, int nt) { return 2 * sc3r_pairs(a, nt) * sc3r_threads(nt); }
 
 }  // namespace
 }  // namespace dnm

@@ -5,14 +5,12 @@
 #include "sc3.h"
 
 #include <algorithm>
-#include <map>
-#include <memory>
-#include <mutex>
 
 #include "dnm_common.h"
 #include "kernels.h"
 #include "philox.h"
 #include "sc3_dev.h"
+#include "sc3_launch.h"
 
 namespace dnm {
 
@@ -985,276 +983,9 @@ sc3_positions_perm_kernel(const Sc3Tab S, const Sc3Perm P, int64_t n, const int6
 }  // namespace
 
 // ===========================================================================================================
-// host side
+// host side: what launches (every table these launches read is built in sc3_tables.cpp)
 // ===========================================================================================================
-static int64_t hbinom(int n, int k) {
-  if (k < 0 || k > n) return 0;
-  long double r = 1;
-  for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i;
-  return (int64_t)llroundl(r);
-}
-
-bool sc3_valid(int L, int k, int a, int w) {
-  const int t = L - a - w;
-  return a >= 2 && a <= SC3_MAXA && w >= 2 && w <= SC3_MAXW && t >= 1 && t <= 15 && k >= 0 && k <= L;
-}
-
-Sc3Layout::~Sc3Layout() {
-  for (void *p : {d_ibase, d_nbase, d_icoff, d_ncoff, d_lo_pat, d_w_pat, d_lo_rank, d_w_rank, d_cbin, d_rows, d_nck, d_w_nb, d_ibase_h, d_icoff_h, d_lo_rlo, d_lo_rhi})
-    if (p) (void)hipFree(p);
-}
-
-template <class T_>
-static int up(const std::vector<T_> &v, void **d) {
-  DNM_HIP(hipMalloc(d, std::max<size_t>(1, v.size()) * sizeof(T_)));
-  DNM_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(T_), hipMemcpyHostToDevice));
-  return 0;
-}
-
-int Sc3Layout::init(int L, int k, int a, int w, bool want_device, int order_) {
-  DNM_CHECK(sc3_valid(L, k, a, w), "no such vector layout: L=%d k=%d a=%d w=%d", L, k, a, w);
-  DNM_CHECK(order_ == 0 || order_ == 1, "unknown block order %d of a SpinConserve layout", order_);
-  order = order_;
-  Sc3Tab &S = host;
-  S = Sc3Tab{};
-  S.L = L; S.k = k; S.a = a; S.w = w; S.t = L - a - w;
-  const int t = S.t;
-  cbin.assign(17 * 17, 0);
-  for (int n = 0; n < 17; ++n) for (int j = 0; j < 17; ++j) cbin[n * 17 + j] = (int32_t)hbinom(n, j);
-  nck.assign((size_t)(k + 1) * (L + 1), 0);
-  for (int kk = 0; kk <= k; ++kk) for (int LL = 0; LL <= L; ++LL) nck[(size_t)kk * (L + 1) + LL] = hbinom(LL, kk);
-  lo_rank.assign((size_t)1 << a, 0);
-  w_rank.assign((size_t)1 << w, 0);
-  lo_pat.clear();
-  w_pat.clear();
-  for (int j = 0; j <= a; ++j) {
-    S.lo_off[j] = (int32_t)lo_pat.size();
-    S.nl[j] = (int32_t)hbinom(a, j);
-    S.pitch[j] = (S.nl[j] + 7) / 8 * 8;
-    int r = 0;
-    for (uint32_t v = 0; v < (1u << a); ++v)
-      if (__builtin_popcount(v) == j) { lo_rank[v] = (uint16_t)r++; lo_pat.push_back((uint16_t)v); }
-  }
-  S.lo_off[a + 1] = (int32_t)lo_pat.size();
-  const int wmax = (int)hbinom(w, w / 2);
-  for (int j = 0; j <= w; ++j) {
-    S.w_off[j] = (int32_t)w_pat.size();
-    S.nw[j] = (int32_t)hbinom(w, j);
-    int r = 0;
-    for (uint32_t v = 0; v < (1u << w); ++v)
-      if (__builtin_popcount(v) == j) { w_rank[v] = (uint16_t)r++; w_pat.push_back((uint16_t)v); }
-    int s = 0;
-    while ((S.nw[j] << (s + 1)) <= wmax && s < 8) ++s;      // R = 16 << s keeps nw * R within the largest tile
-    S.rs[j] = s;
-  }
-  S.w_off[w + 1] = (int32_t)w_pat.size();
-  // partner table of the window pass's LDS bonds (Sc3Tab::w_nb)
-  // (only the field splits that have kernel instances need them; wider ones keep the tables empty)
-  const bool nbfit = w - 1 <= 16 && hbinom(w, w / 2) < 255;
-  w_nb.assign(nbfit ? (size_t)2 * w_pat.size() : 0, 0);
-  for (int j = 0; nbfit && j <= w; ++j)
-    for (int r = 0; r < S.nw[j]; ++r) {
-      const uint32_t v = w_pat[S.w_off[j] + r];
-      for (int b = 0; b < 16; ++b) {
-        uint64_t f = (uint64_t)S.nw[j];                        // the zero row
-        if (b < w - 1) {
-          const uint32_t pair = (v >> b) & 3u;
-          if (pair == 1u || pair == 2u) f = w_rank[v ^ (3u << b)];
-        }
-        w_nb[(size_t)2 * (S.w_off[j] + r) + (size_t)(b / 8)] |= f << (8 * (b % 8));
-      }
-    }
-  // lo_rank in two halves (Sc3Tab::lo_rlo / lo_rhi): colex rank = sum over the ones, m-th one at position q: C(q, m)
-  {
-    const int h = a / 2, hb = a - h;
-    lo_rlo.assign((size_t)1 << h, 0);
-    lo_rhi.assign(((size_t)1 << hb) * (h + 1), 0);
-    for (uint32_t v = 0; v < (1u << h); ++v) {
-      int64_t r = 0;
-      int m = 0;
-      for (int q = 0; q < h; ++q) if ((v >> q) & 1u) r += hbinom(q, ++m);
-      lo_rlo[v] = (uint16_t)r;
-    }
-    for (uint32_t v = 0; v < (1u << hb); ++v)
-      for (int cl = 0; cl <= h; ++cl) {
-        int64_t r = 0;
-        int m = cl;
-        for (int q = 0; q < hb; ++q) if ((v >> q) & 1u) r += hbinom(h + q, ++m);
-        lo_rhi[(size_t)v * (h + 1) + cl] = (uint16_t)r;
-      }
-    for (uint32_t v = 0; v < (1u << a); ++v) {
-      const uint32_t lo = v & ((1u << h) - 1u);
-      DNM_CHECK(lo_rank[v] == lo_rlo[lo] + lo_rhi[(size_t)(v >> h) * (h + 1) + __builtin_popcount(lo)],
-                "internal: split rank table of pattern %u", v);
-    }
-  }
-  icoff.assign((size_t)(a + w + 1) * (w + 1), 0);
-  ncoff.assign((size_t)(a + w + 1) << w, 0);
-  std::vector<int64_t> isize(a + w + 1, 0);
-  for (int kr = 0; kr <= a + w; ++kr) {
-    int64_t o = 0;
-    for (int cw = 0; cw <= w; ++cw) {
-      icoff[(size_t)kr * (w + 1) + cw] = o;
-      const int kl = kr - cw;
-      if (kl >= 0 && kl <= a) o += hbinom(w, cw) * S.pitch[kl];
-    }
-    isize[kr] = o;
-    int64_t no = 0;
-    for (uint32_t W = 0; W < (1u << w); ++W) {
-      ncoff[((size_t)kr << w) + W] = no;
-      const int kl = kr - __builtin_popcount(W);
-      if (kl >= 0 && kl <= a) no += hbinom(a, kl);
-    }
-  }
-  ibase.assign((size_t)1 << t, -1);
-  nbase.assign((size_t)1 << t, -1);
-  rows.clear();
-  int64_t ni = 0, nn = 0;
-  // reference indices: ascending T
-  tseq.clear();
-  for (uint32_t T = 0; T < (1u << t); ++T) {
-    const int kr = k - __builtin_popcount(T);
-    if (kr < 0 || kr > a + w) continue;
-    nbase[T] = nn;
-    nn += hbinom(a + w, kr);
-    tseq.push_back(T);
-  }
-  // the order the blocks lie in (sc3_code_order)
-  if (order == 1) {
-    // by (ones of T above its lowest bit, ones of T's upper half, T >> 1, T & 1): the two blocks that differ in T's lowest
-    // bit -- partners under the W/T boundary bond -- lie side by side, the bonds inside T >> 1 keep the first key, and of
-    // a chain's bonds only the one between T's two lowest bits changes it (sc3.h: sc3_code_order)
-    const int th = t / 2;
-    std::stable_sort(tseq.begin(), tseq.end(), [th](uint32_t x, uint32_t y) {
-      const int px = __builtin_popcount(x >> 1), py = __builtin_popcount(y >> 1);
-      if (px != py) return px < py;
-      const int hx = __builtin_popcount(x >> th), hy = __builtin_popcount(y >> th);
-      if (hx != hy) return hx < hy;
-      return x < y;                    // (T >> 1, then T & 1)
-    });
-  }
-  tidx.assign((size_t)1 << t, 0xffffffffu);
-  rowstart.assign(tseq.size() + 1, 0);
-  for (size_t b = 0; b < tseq.size(); ++b) {
-    const uint32_t T = tseq[b];
-    const int kr = k - __builtin_popcount(T);
-    tidx[T] = (uint32_t)b;
-    ibase[T] = ni;
-    ni += isize[kr];
-    rowstart[b] = rows.size();
-    for (uint32_t W = 0; W < (1u << w); ++W) {
-      const int kl = kr - __builtin_popcount(W);
-      if (kl >= 0 && kl <= a) rows.push_back((T << w) | W);
-    }
-  }
-  rowstart[tseq.size()] = rows.size();
-  S.nint = ni;
-  dim = nn;
-  DNM_CHECK(nn == hbinom(L, k), "internal: layout does not cover the subspace");
-  S.ibase = ibase.data(); S.nbase = nbase.data(); S.icoff = icoff.data(); S.ncoff = ncoff.data();
-  S.lo_pat = lo_pat.data(); S.w_pat = w_pat.data(); S.lo_rank = lo_rank.data(); S.w_rank = w_rank.data();
-  S.cbin = cbin.data();
-  S.nck = nck.data();
-  S.w_nb = w_nb.data();
-  S.lo_rlo = lo_rlo.data();
-  S.lo_rhi = lo_rhi.data();
-  dev = S;
-  // halved positions (real vectors read as pairs of entries): everything is a multiple of 8 entries
-  ibase_h.assign(ibase.size(), -1);
-  for (size_t i = 0; i < ibase.size(); ++i) if (ibase[i] >= 0) ibase_h[i] = ibase[i] / 2;
-  icoff_h.assign(icoff.size(), 0);
-  for (size_t i = 0; i < icoff.size(); ++i) icoff_h[i] = icoff[i] / 2;
-  host_h = S;
-  host_h.ibase = ibase_h.data();
-  host_h.icoff = icoff_h.data();
-  host_h.nint = S.nint / 2;
-  for (int j = 0; j <= a; ++j) host_h.pitch[j] = S.pitch[j] / 2;
-  if (want_device) {
-    DNM_TRY(up(ibase, &d_ibase)); DNM_TRY(up(nbase, &d_nbase)); DNM_TRY(up(icoff, &d_icoff));
-    DNM_TRY(up(ncoff, &d_ncoff)); DNM_TRY(up(lo_pat, &d_lo_pat)); DNM_TRY(up(w_pat, &d_w_pat));
-    DNM_TRY(up(lo_rank, &d_lo_rank)); DNM_TRY(up(w_rank, &d_w_rank)); DNM_TRY(up(cbin, &d_cbin));
-    DNM_TRY(up(rows, &d_rows));
-    DNM_TRY(up(nck, &d_nck));
-    DNM_TRY(up(w_nb, &d_w_nb));
-    dev.w_nb = (const uint64_t *)d_w_nb;
-    DNM_TRY(up(lo_rlo, &d_lo_rlo)); DNM_TRY(up(lo_rhi, &d_lo_rhi));
-    dev.lo_rlo = (const uint16_t *)d_lo_rlo; dev.lo_rhi = (const uint16_t *)d_lo_rhi;
-    dev.ibase = (const int64_t *)d_ibase; dev.nbase = (const int64_t *)d_nbase;
-    dev.icoff = (const int64_t *)d_icoff; dev.ncoff = (const int64_t *)d_ncoff;
-    dev.lo_pat = (const uint16_t *)d_lo_pat; dev.w_pat = (const uint16_t *)d_w_pat;
-    dev.lo_rank = (const uint16_t *)d_lo_rank; dev.w_rank = (const uint16_t *)d_w_rank;
-    dev.cbin = (const int32_t *)d_cbin;
-    dev.nck = (const int64_t *)d_nck;
-    DNM_TRY(up(ibase_h, &d_ibase_h)); DNM_TRY(up(icoff_h, &d_icoff_h));
-    dev_h = dev;
-    dev_h.ibase = (const int64_t *)d_ibase_h;
-    dev_h.icoff = (const int64_t *)d_icoff_h;
-    dev_h.nint = host_h.nint;
-    for (int j = 0; j <= a; ++j) dev_h.pitch[j] = host_h.pitch[j];
-    on_device = true;
-  }
-  return 0;
-}
-
-const Sc3Layout *sc3_get(int L, int k, int a, int w, bool want_device, int order) {
-  static std::mutex mu;
-  static std::map<std::array<int, 6>, std::unique_ptr<Sc3Layout>> cache;
-  std::lock_guard<std::mutex> g(mu);
-  const std::array<int, 6> key{L, k, a, w, want_device ? 1 : 0, order};
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second.get();
-  std::unique_ptr<Sc3Layout> lay(new Sc3Layout());
-  if (lay->init(L, k, a, w, want_device, order)) return nullptr;
-  return (cache[key] = std::move(lay)).get();
-}
-
-// ---- utilities ------------------------------------------------------------------------------------------
-// the rows of the T blocks [T0, T1) inside Ly.rows (sorted by T, then W) and the offsets of that range
-struct RowRange { size_t first, count; int64_t ioff, noff; };
-static RowRange row_range(const Sc3Layout &Ly, uint32_t T0, uint32_t T1) {
-  const uint32_t nb = (uint32_t)Ly.tseq.size();
-  const uint32_t b0 = std::min(T0, nb), b1 = std::max(b0, std::min(T1, nb));
-  RowRange r;
-  r.first = Ly.rowstart[b0];
-  r.count = Ly.rowstart[b1] - Ly.rowstart[b0];
-  int64_t il, nl;
-  sc3_range(Ly, T0, T1, &r.ioff, &il, &r.noff, &nl);
-  return r;
-}
-// the maps between a layout and the reference order need the range's reference side to be a range too: every range of
-// block order 0, whole vectors of the others
-static int ref_side(const Sc3Layout &Ly, const RowRange &r) {
-  DNM_CHECK(Ly.order == 0 || (r.first == 0 && r.count == Ly.rows.size()),
-            "a rank's share of a SpinConserve layout in block order %d is no range of the reference order", Ly.order);
-  return 0;
-}
-
-bool sc3_perm_make(const int8_t *site_perm, int L, Sc3Perm *out) {
-  *out = Sc3Perm{};
-  out->L = L;
-  for (int i = 0; i < 64; ++i) out->to_int[i] = out->to_ref[i] = (uint8_t)i;
-  if (!site_perm) return true;
-  uint64_t seen = 0;
-  for (int i = 0; i < L; ++i) {
-    const int b = site_perm[i];
-    if (b < 0 || b >= L || ((seen >> b) & 1ull)) return false;
-    seen |= 1ull << b;
-    out->to_int[i] = (uint8_t)b;
-    out->to_ref[b] = (uint8_t)i;
-    if (b != i) out->on = 1;
-  }
-  return true;
-}
-
-// a relabelled layout covers whole vectors on one rank
-static int perm_whole(const Sc3Layout &Ly, const Sc3Perm *perm, const RowRange &r) {
-  // (whole vectors, or the blocks below a bound -- the half whose top bit is clear, an XParity vector: both start at
-  // position 0 of the layout and at index 0 of the reference order)
-  DNM_CHECK(!perm || !perm->on || (r.first == 0 && r.ioff == 0 && r.noff == 0),
-            "a relabelled SpinConserve layout is not partitioned over ranks");
-  return 0;
-}
-
+// ---- the layout's vector utilities --------------------------------------------------------------------------
 int sc3_layout_copy(const Sc3Layout &Ly, void *dst, const void *src, bool to_internal, hipStream_t st, uint32_t T0, uint32_t T1,
                     const Sc3Perm *perm) {
   DNM_CHECK(Ly.on_device, "layout tables are not on the device");
@@ -1264,12 +995,12 @@ int sc3_layout_copy(const Sc3Layout &Ly, void *dst, const void *src, bool to_int
   DNM_TRY(ref_side(Ly, r));
   if (perm && perm->on) {
     hipLaunchKernelGGL(sc3_copy_perm_kernel<c128>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev, *perm,
-                       (const uint32_t *)Ly.d_rows, (c128 *)dst, (const c128 *)src, to_internal ? 1 : 0);
+                       Ly.d_rows.as<uint32_t>(), (c128 *)dst, (const c128 *)src, to_internal ? 1 : 0);
     DNM_HIP(hipGetLastError());
     return 0;
   }
   hipLaunchKernelGGL(sc3_copy_kernel<c128>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev,
-                     (const uint32_t *)Ly.d_rows + r.first, (c128 *)dst, (const c128 *)src, to_internal ? 1 : 0, r.ioff, r.noff);
+                     Ly.d_rows.as<uint32_t>() + r.first, (c128 *)dst, (const c128 *)src, to_internal ? 1 : 0, r.ioff, r.noff);
   DNM_HIP(hipGetLastError());
   return 0;
 }
@@ -1282,12 +1013,12 @@ int sc3_layout_copy_f64(const Sc3Layout &Ly, double *dst, const double *src, boo
   DNM_TRY(ref_side(Ly, r));
   if (perm && perm->on) {
     hipLaunchKernelGGL(sc3_copy_perm_kernel<double>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev, *perm,
-                       (const uint32_t *)Ly.d_rows, dst, src, to_internal ? 1 : 0);
+                       Ly.d_rows.as<uint32_t>(), dst, src, to_internal ? 1 : 0);
     DNM_HIP(hipGetLastError());
     return 0;
   }
   hipLaunchKernelGGL(sc3_copy_kernel<double>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev,
-                     (const uint32_t *)Ly.d_rows + r.first, dst, src, to_internal ? 1 : 0, r.ioff, r.noff);
+                     Ly.d_rows.as<uint32_t>() + r.first, dst, src, to_internal ? 1 : 0, r.ioff, r.noff);
   DNM_HIP(hipGetLastError());
   return 0;
 }
@@ -1296,7 +1027,7 @@ int sc3_zero_padding(const Sc3Layout &Ly, void *x, hipStream_t st, uint32_t T0, 
   const RowRange r = row_range(Ly, T0, T1);
   if (!r.count) return 0;
   hipLaunchKernelGGL(sc3_zero_pad_kernel, dim3((unsigned)r.count), dim3(64), 0, st, Ly.dev,
-                     (const uint32_t *)Ly.d_rows + r.first, (c128 *)x, r.ioff);
+                     Ly.d_rows.as<uint32_t>() + r.first, (c128 *)x, r.ioff);
   DNM_HIP(hipGetLastError());
   return 0;
 }
@@ -1307,12 +1038,12 @@ int sc3_random(const Sc3Layout &Ly, void *x, uint64_t seed, hipStream_t st, uint
   DNM_TRY(perm_whole(Ly, perm, r));
   if (perm && perm->on) {
     hipLaunchKernelGGL(sc3_random_perm_kernel<false>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev, *perm,
-                       (const uint32_t *)Ly.d_rows, x, seed);
+                       Ly.d_rows.as<uint32_t>(), x, seed);
     DNM_HIP(hipGetLastError());
     return 0;
   }
   hipLaunchKernelGGL(sc3_random_kernel, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev,
-                     (const uint32_t *)Ly.d_rows + r.first, (c128 *)x, seed, r.ioff);
+                     Ly.d_rows.as<uint32_t>() + r.first, (c128 *)x, seed, r.ioff);
   DNM_HIP(hipGetLastError());
   return 0;
 }
@@ -1324,12 +1055,12 @@ int sc3_random_real(const Sc3Layout &Ly, double *x, uint64_t seed, hipStream_t s
   DNM_TRY(perm_whole(Ly, perm, r));
   if (perm && perm->on) {
     hipLaunchKernelGGL(sc3_random_perm_kernel<true>, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev, *perm,
-                       (const uint32_t *)Ly.d_rows, (void *)x, seed);
+                       Ly.d_rows.as<uint32_t>(), (void *)x, seed);
     DNM_HIP(hipGetLastError());
     return 0;
   }
   hipLaunchKernelGGL(sc3_random_real_kernel, dim3((unsigned)r.count), dim3(256), 0, st, Ly.dev,
-                     (const uint32_t *)Ly.d_rows + r.first, x, seed, r.ioff);
+                     Ly.d_rows.as<uint32_t>() + r.first, x, seed, r.ioff);
   DNM_HIP(hipGetLastError());
   return 0;
 }
@@ -1361,574 +1092,26 @@ int sc3_positions(const Sc3Layout &Ly, int64_t n, const int64_t *idx, int64_t *p
   return 0;
 }
 
-// ---- the operator ---------------------------------------------------------------------------------------
-// deal groups of workgroups to the 8 XCDs (workgroup b runs on XCD b % 8): the next group goes to the shortest stream
-static std::vector<uint32_t> deal(const std::vector<std::vector<uint32_t>> &groups) {
-  std::vector<std::vector<uint32_t>> st(8);
-  for (auto &g : groups) {
-    int best = 0;
-    for (int s = 1; s < 8; ++s) if (st[s].size() < st[best].size()) best = s;
-    st[best].insert(st[best].end(), g.begin(), g.end());
-  }
-  size_t n = 0;
-  for (auto &s : st) n = std::max(n, s.size());
-  std::vector<uint32_t> out(8 * n, 0xffffffffu);
-  for (int s = 0; s < 8; ++s)
-    for (size_t i = 0; i < st[s].size(); ++i) out[8 * i + s] = st[s][i];
-  return out;
-}
-
-// lo pass: rows -> workgroups.  `order` is the dispatch order of the rows (8 interleaved XCD streams, 0xffffffff =
-// padding); inside a stream rows are packed, in that order, 2^m to a workgroup where 2^m rows of their length fit the
-// NT * RPT entries a workgroup's threads hold (sub-groups of whole wavefronts, m <= 3).  Rows that follow each other in
-// a stream are the same (cw, wr) over the T's of a popcount class, so a workgroup's rows have equal lengths and its
-// place in the stream stays next to the boundary-bond partners of its rows.  Returns 8 entries per workgroup, the
-// workgroups of the streams interleaved again.
-static std::vector<uint32_t> pack_lo_rows(const std::vector<uint32_t> &order, const Sc3Layout &ly, int nt, bool real) {
-  const Sc3Tab &S = ly.host;
-  const int cap = real ? sc3_lo_cap_r(S.a, nt) : sc3_lo_cap(S.a, nt);      // entries a workgroup's threads hold
-  if (real) nt = sc3r_threads(nt);
-  int maxm = 0;
-  while (maxm < 3 && (nt >> (maxm + 1)) >= 64) ++maxm;
-  auto logm_of = [&](uint32_t e) {
-    const uint32_t T = e >> S.w, W = e & ((1u << S.w) - 1u);
-    const int kl = S.k - __builtin_popcount(T) - __builtin_popcount(W);
-    int m = 0;
-    while (m < maxm && S.nl[kl] <= (cap >> (m + 1))) ++m;
-    return m;
-  };
-  std::vector<std::vector<uint32_t>> wgs(8);        // per stream: 8 entries per workgroup
-  for (int s = 0; s < 8; ++s) {
-    std::vector<uint32_t> open[4];                  // rows waiting for their workgroup to fill, by m
-    auto flush = [&](int m) {
-      if (open[m].empty()) return;
-      for (int j = 0; j < 8; ++j)
-        wgs[s].push_back(j < (int)open[m].size() ? (open[m][j] | ((uint32_t)m << 30)) : (SC3_NOROW | ((uint32_t)m << 30)));
-      open[m].clear();
-    };
-    for (size_t i = s; i < order.size(); i += 8) {
-      const uint32_t e = order[i];
-      if (e == 0xffffffffu) continue;
-      const int m = logm_of(e);
-      open[m].push_back(e);
-      if ((int)open[m].size() == (1 << m)) flush(m);
-    }
-    for (int m = 0; m < 4; ++m) flush(m);
-  }
-  size_t n = 0;
-  for (auto &v : wgs) n = std::max(n, v.size() / 8);
-  std::vector<uint32_t> out(8 * 8 * n, 0xffffffffu);
-  for (int s = 0; s < 8; ++s)
-    for (size_t i = 0; i < wgs[s].size() / 8; ++i)
-      for (int j = 0; j < 8; ++j) out[8 * (8 * i + s) + j] = wgs[s][8 * i + j];
-  return out;
-}
-
-bool sc3_instance(int a, int w) { return (a == 14 && w == 10) || (a == 6 && w == 4); }
-
-Sc3Mat::~Sc3Mat() {
-  for (void *p : {d_permA, d_permB, d_bond, d_dlo, d_dt_sign, d_dt_coef, d_dt_group, d_rowsel, d_hops, d_wnb, d_ptab, d_pcoef})
-    if (p) (void)hipFree(p);
-}
-
-static int64_t block_len(const Sc3Layout &ly, uint32_t T) {        // internal length of the T block
-  if (ly.ibase[T] < 0) return 0;
-  const uint32_t b = ly.tidx[T];                                     // (the next block of the layout's sequence, whatever its order)
-  return (b + 1 < (uint32_t)ly.tseq.size() ? ly.ibase[ly.tseq[b + 1]] : ly.host.nint) - ly.ibase[T];
-}
-
-std::vector<uint32_t> sc3_partition(const Sc3Layout &ly, int nranks) {
-  const uint32_t nb = (uint32_t)ly.tseq.size();
-  std::vector<uint32_t> Tb((size_t)nranks + 1, nb);
-  Tb[0] = 0;
-  uint32_t b = 0;
-  for (int r = 1; r < nranks; ++r) {
-    const int64_t target = (int64_t)((__int128)ly.host.nint * r / nranks);
-    while (b < nb && ly.ibase[ly.tseq[b]] < target) ++b;
-    Tb[r] = b;
-  }
-  return Tb;
-}
-
-void sc3_range(const Sc3Layout &ly, uint32_t T0, uint32_t T1, int64_t *istart, int64_t *ilen, int64_t *nstart, int64_t *nlen) {
-  const uint32_t nb = (uint32_t)ly.tseq.size();
-  const uint32_t b0 = std::min(T0, nb), b1 = std::max(b0, std::min(T1, nb));
-  const int64_t i0 = b0 < nb ? ly.ibase[ly.tseq[b0]] : ly.host.nint, i1 = b1 < nb ? ly.ibase[ly.tseq[b1]] : ly.host.nint;
-  *istart = i0;
-  *ilen = i1 - i0;
-  if (ly.order == 0) {
-    const int64_t n0 = b0 < nb ? ly.nbase[ly.tseq[b0]] : ly.dim, n1 = b1 < nb ? ly.nbase[ly.tseq[b1]] : ly.dim;
-    *nstart = n0;
-    *nlen = n1 - n0;
-    return;
-  }
-  // any other block order: the states of the range (its reference side is a range only for the whole sequence)
-  int64_t n = 0;
-  const int aw = ly.host.a + ly.host.w;
-  for (uint32_t b = b0; b < b1; ++b) n += hbinom(aw, ly.host.k - __builtin_popcount(ly.tseq[b]));
-  *nstart = b0 == 0 ? 0 : -1;
-  *nlen = n;
-}
-
-void Sc3Mat::window(int64_t *lo, int64_t *hi) const {
-  int64_t a = INT64_MAX, b = INT64_MIN;
-  for (uint32_t T = 0; T < (uint32_t)needT.size(); ++T)
-    if (needT[T] && ly->ibase[T] >= 0) {
-      a = std::min(a, ly->ibase[T]);
-      b = std::max(b, ly->ibase[T] + block_len(*ly, T) - 1);
-    }
-  if (b < a) a = b = row0;
-  *lo = a;
-  *hi = b;
-}
-
-// the needed blocks as maximal runs of positions [lo, hi), ascending
-std::vector<std::pair<int64_t, int64_t>> Sc3Mat::ranges() const {
-  std::vector<std::pair<int64_t, int64_t>> blk;
-  for (uint32_t T = 0; T < (uint32_t)needT.size(); ++T)
-    if (needT[T] && ly->ibase[T] >= 0) blk.push_back({ly->ibase[T], ly->ibase[T] + block_len(*ly, T)});
-  std::sort(blk.begin(), blk.end());
-  std::vector<std::pair<int64_t, int64_t>> out;
-  for (const auto &b : blk) {
-    if (!out.empty() && out.back().second == b.first) out.back().second = b.second;
-    else out.push_back(b);
-  }
-  return out;
-}
-
-void Sc3Mat::chunks(int shift, int64_t first_chunk, int64_t nchunks, uint8_t *map) const {
-  for (int64_t c = 0; c < nchunks; ++c) map[c] = 0;
-  for (uint32_t T = 0; T < (uint32_t)needT.size(); ++T)
-    if (needT[T] && ly->ibase[T] >= 0) {
-      const int64_t c0 = (ly->ibase[T] >> shift) - first_chunk, c1 = ((ly->ibase[T] + block_len(*ly, T) - 1) >> shift) - first_chunk;
-      for (int64_t c = std::max<int64_t>(c0, 0); c <= c1 && c < nchunks; ++c) map[c] = 1;
-    }
-}
-
-int Sc3Mat::init(const Sc3Layout *layout, const std::vector<int64_t> &masks, const std::vector<int64_t> &mask_offsets,
-                 const std::vector<int64_t> &signs, const std::vector<double> &rcoef, const std::vector<ScMask> &scm,
-                 bool want_device, uint32_t T0_, uint32_t T1_, bool real_vectors) {
-  ly = layout;
-  real = real_vectors;
-  T0 = T0_;
-  T1 = T1_;
-  const Sc3Tab &S = ly->host;
-  const int L = S.L, a = S.a, w = S.w, t = S.t, k = S.k;
-  const int64_t nmasks = (int64_t)masks.size();
-  {
-    int64_t il, ns, nl;
-    sc3_range(*ly, T0, T1, &row0, &il, &ns, &nl);
-  }
-  rowsel.clear();
-  {
-    const uint32_t nb = (uint32_t)ly->tseq.size();
-    const uint32_t b0 = std::min(T0, nb), b1 = std::max(b0, std::min(T1, nb));
-    rowsel.assign(ly->rows.begin() + (ptrdiff_t)ly->rowstart[b0], ly->rows.begin() + (ptrdiff_t)ly->rowstart[b1]);
-  }
-  if (rowsel.empty()) rowsel.push_back(0xffffffffu);
-  if (want_device) DNM_TRY(up(rowsel, &d_rowsel));
-  // the T blocks these rows read: their own and, for every mask that flips bits of T, the partner's
-  needT.assign((size_t)1 << t, 0);
-  for (uint32_t bq = T0; bq < T1 && bq < (uint32_t)ly->tseq.size(); ++bq) {
-    const uint32_t T = ly->tseq[bq];
-    needT[T] = 1;
-    for (int64_t m = 0; m < nmasks; ++m) {
-      const uint64_t hm = (uint64_t)masks[m] >> (a + w);
-      const uint32_t U = T ^ (uint32_t)hm;
-      if (!hm || U >= (1u << t) || ly->ibase[U] < 0) continue;     // (a mask that leaves T alone reads T itself)
-      // a mask that flips bits of T only keeps the state in the subspace only if it keeps T's popcount
-      const bool inside_T = ((uint64_t)masks[m] & (((uint64_t)1 << (a + w)) - 1)) == 0;
-      if (inside_T && __builtin_popcount(U) != __builtin_popcount(T)) continue;
-      needT[U] = 1;
-    }
-  }
-  // Two tiled passes need every off-diagonal mask to be a pair hop with signs inside the pair (ScMask::pair); masks
-  // that never keep a state in the subspace (an odd number of flips: the fields of the harness's long-range model)
-  // are skipped.  Chains of adjacent spins take the kernels of this file, any other bond graph those of
-  // sc3g_kernels.hip (DNM_SC3_GRAPH=1: chains as well, for A/B runs).
-  bool chain = sc3_instance(a, w), pairs = sc3_instance(a, w);
-  for (int64_t m = 0; m < nmasks; ++m) {
-    if (masks[m] == 0 || scm[m].dead) continue;
-    if (!scm[m].fast) chain = false;
-    if (!scm[m].pair) pairs = false;
-  }
-  if (const char *e = knob("DNM_SC3_GRAPH")) if (e[0] == '1') chain = false;
-  tiled = chain || pairs;
-  graph = tiled && !chain;
-  if (!tiled) return 0;
-  std::vector<double> bond(4 * (size_t)std::max(1, L - 1), 0.0);
-  op.present = 0;
-  sym = true;
-  for (int64_t m = 0; m < nmasks; ++m) {
-    if (masks[m] == 0 || scm[m].dead) continue;
-    if (scm[m].up_im != 0.0 || scm[m].dn_im != 0.0 || scm[m].up_re != scm[m].dn_re) sym = false;
-    if (graph) continue;
-    const int b = scm[m].lo;
-    bond[4 * b] = scm[m].up_re; bond[4 * b + 1] = scm[m].up_im;
-    bond[4 * b + 2] = scm[m].dn_re; bond[4 * b + 3] = scm[m].dn_im;
-    op.present |= 1ull << b;
-  }
-  // which pass gathers which bond outside its LDS tile: the Lo/W boundary in the lo pass, the W/T boundary and the
-  // bonds inside T in the window pass (measured, profiles/r03_exp3_sc3_v2.txt)
-  op.bondsA = op.present & (1ull << (a - 1));
-  op.bondsB = 0;
-  for (int b = a + w - 1; b < L - 1; ++b) op.bondsB |= op.present & (1ull << b);
-  // any bond graph: the hops by pass and by the way they are applied
-  hops.clear();
-  wnb.clear();
-  size_t nh[4] = {0, 0, 0, 0};
-  if (graph) {
-    std::vector<Sc3Hop> part[4];       // lds A, gathered A, lds B, gathered B
-    auto field = [&](int b) { return b < a ? 0 : (b < a + w ? 1 : 2); };
-    auto fstart = [&](int f) { return f == 0 ? 0 : (f == 1 ? a : a + w); };
-    for (int64_t m = 0; m < nmasks; ++m) {
-      if (masks[m] == 0 || scm[m].dead) continue;
-      const uint64_t mk = (uint64_t)masks[m];
-      Sc3Hop h{};
-      h.mLo = (uint32_t)(mk & (((uint64_t)1 << a) - 1));
-      h.mW = (uint32_t)((mk >> a) & (((uint64_t)1 << w) - 1));
-      h.mT = (uint32_t)(mk >> (a + w));
-      h.half = __builtin_popcountll(mk) / 2;
-      const int fi = field(scm[m].lo), fj = field(scm[m].hi);
-      h.dfield = scm[m].pair == 2 ? 3 : fi;      // (the flip-composed hops of XParity act one way only)
-      h.dbit = scm[m].lo - fstart(fi);
-      h.up_re = scm[m].up_re; h.up_im = scm[m].up_im; h.dn_re = scm[m].dn_re; h.dn_im = scm[m].dn_im;
-      part[fi == 0 ? (fj == 0 ? 0 : 1) : (fi == 1 && fj == 1 ? 2 : 3)].push_back(h);
-    }
-    // probes (timing only, WRONG results): keep the first n hops of a kind -- what a pass would take without the others
-    // bounds what any reworking of them can gain (tools/probes/sc3g_drop_hops.sh)
-    for (int q = 0; q < 4; ++q) {
-      static const char *names[4] = {"DNM_SC3G_KEEP_LDSA", "DNM_SC3G_KEEP_GATA", "DNM_SC3G_KEEP_LDSB", "DNM_SC3G_KEEP_GATB"};
-      if (const char *e = knob(names[q]))
-        if ((size_t)atoi(e) < part[q].size()) part[q].resize((size_t)atoi(e));
-    }
-    if ((int)part[1].size() > SC3G_MAX_GATHER || (int)part[3].size() > SC3G_MAX_GATHER ||
-        (int)part[2].size() > SC3G_MAX_WLDS) {      // more hops than a pass has lanes / table columns for: the row kernel
-      tiled = graph = false;
-      return 0;
-    }
-    for (int q = 0; q < 4; ++q) {
-      nh[q] = part[q].size();
-      hops.insert(hops.end(), part[q].begin(), part[q].end());
-    }
-    if (hops.empty()) hops.push_back(Sc3Hop{});
-    // partner rows of the window pass's LDS hops
-    const size_t nb = nh[2];
-    wnb.assign(std::max<size_t>(1, ly->w_pat.size() * nb), 0);
-    for (int cw = 0; cw <= w; ++cw)
-      for (int wr = 0; wr < S.nw[cw]; ++wr) {
-        const uint32_t v = ly->w_pat[S.w_off[cw] + wr];
-        for (size_t q = 0; q < nb; ++q) {
-          const uint32_t mw = part[2][q].mW;
-          wnb[(size_t)(S.w_off[cw] + wr) * nb + q] =
-              (uint8_t)(__builtin_popcount(v & mw) == part[2][q].half ? ly->w_rank[v ^ mw] : S.nw[cw]);
-        }
-      }
-  }
-  op.nldsA = (int32_t)nh[0]; op.ngatA = (int32_t)nh[1]; op.nldsB = (int32_t)nh[2]; op.ngatB = (int32_t)nh[3];
-  // partner table of the lo pass's LDS hops (Sc3Op::ptab).  Needs the zero entry behind a row's entries inside the
-  // row's share of the tile: true for every class of the instances (C(a, kl) is no power of two above 1).
-  ptab.clear();
-  op.ptab = nullptr;
-  op.nhp = 0;
-  {
-    const char *pe = knob("DNM_SC3G_PTAB");
-    const int ntl = a == 14 ? 1024 : 256;          // threads of the lo pass (launch_sc3g)
-    const int cap = real ? sc3_lo_cap_r(a, ntl) : sc3_lo_cap(a, ntl);
-    const int nthr = real ? sc3r_threads(ntl) : ntl;
-    int maxm = 0;
-    while (maxm < 3 && (nthr >> (maxm + 1)) >= 64) ++maxm;
-    bool ok = graph && nh[0] > 0 && (int)nh[0] <= SC3G_MAX_PTAB && !(pe && pe[0] == '0');
-    for (int kl = 0; kl <= a && ok; ++kl) {
-      int m = 0;
-      while (m < maxm && S.nl[kl] <= (cap >> (m + 1))) ++m;
-      if (S.nl[kl] >= (cap >> m) || (S.nl[kl] + 1) * (real ? 8 : 16) > 0xffff) ok = false;
-    }
-    if (ok) {
-      const int nhp = ((int)nh[0] + 7) & ~7, esz = real ? 8 : 16;
-      int row = 0;
-      for (int kl = 0; kl <= a; ++kl) {
-        op.ptab_row[kl] = row;
-        row += (S.nl[kl] + 2) & ~1;
-      }
-      ptab.assign((size_t)row * nhp, 0);
-      for (int kl = 0; kl <= a; ++kl) {
-        const uint16_t zero = (uint16_t)(S.nl[kl] * esz);
-        const int nrow = (S.nl[kl] + 2) & ~1;
-        for (int r = 0; r < nrow; ++r) {
-          uint16_t *t = ptab.data() + (size_t)(op.ptab_row[kl] + r) * nhp;
-          for (int q = 0; q < nhp; ++q) t[q] = zero;
-          if (r >= S.nl[kl]) continue;
-          const uint32_t v = ly->lo_pat[S.lo_off[kl] + r];
-          for (size_t q = 0; q < nh[0]; ++q) {
-            const Sc3Hop &h = hops[q];               // (the LDS hops of the lo pass come first)
-            if (__builtin_popcount(v & h.mLo) == h.half) t[q] = (uint16_t)(ly->lo_rank[v ^ h.mLo] * esz);
-          }
-        }
-      }
-      op.nhp = nhp;
-      pcoef.assign((size_t)nhp, 0.0);
-      for (size_t q = 0; q < nh[0]; ++q) pcoef[q] = hops[q].up_re;
-    }
-  }
-  // diagonal on the fly: split the mask-0 terms by what their sign masks see
-  diag_mode = 0;
-  std::vector<double> dlo;
-  std::vector<uint64_t> dt_sign;
-  std::vector<double> dt_coef;
-  std::vector<int32_t> dt_group;
-  op.ngroups = 0;
-  if (nmasks > 0 && masks[0] == 0) {
-    diag_mode = 2;
-    const uint64_t lom = ((uint64_t)1 << a) - 1;
-    dlo.assign(ly->lo_pat.size(), 0.0);
-    std::vector<uint64_t> groups;
-    for (int64_t tt = mask_offsets[0]; tt < mask_offsets[1]; ++tt) {
-      const uint64_t sg = (uint64_t)signs[tt];
-      const double c = rcoef[tt];
-      if ((sg & ~lom) == 0) {
-        for (size_t i = 0; i < ly->lo_pat.size(); ++i)
-          dlo[i] += (__builtin_popcountll(ly->lo_pat[i] & sg) & 1) ? -c : c;
-        continue;
-      }
-      int g = 0;
-      if (sg & lom) {
-        size_t j = 0;
-        while (j < groups.size() && groups[j] != (sg & lom)) ++j;
-        if (j == groups.size()) groups.push_back(sg & lom);
-        g = (int)j + 1;
-      }
-      dt_sign.push_back((sg >> a) | ((uint64_t)g << 61));
-      dt_coef.push_back(c);
-      dt_group.push_back(g);
-    }
-    if (groups.size() > 4) diag_mode = 1;      // too many mixed patterns: the cached diagonal instead
-    else {
-      op.ngroups = (int32_t)groups.size();
-      for (size_t j = 0; j < groups.size(); ++j) op.glo[j] = (uint32_t)groups[j];
-    }
-  }
-  op.ndt = diag_mode == 2 ? (int32_t)dt_sign.size() : 0;
-  // dispatch order: workgroups that gather from each other run on one XCD at one time (their requests meet in that
-  // XCD's L2).  Window pass: groups (kt, cw, run) over the T's of a popcount class -- siblings under the T bonds.
-  std::vector<std::vector<uint32_t>> Tby(t + 1), gA, gB;
-  for (uint32_t bq = T0; bq < T1 && bq < (uint32_t)ly->tseq.size(); ++bq) Tby[__builtin_popcount(ly->tseq[bq])].push_back(ly->tseq[bq]);
-  for (auto &v : Tby) std::sort(v.begin(), v.end());
-  for (int kt = 0; kt <= t; ++kt) {
-    if (Tby[kt].empty()) continue;
-    const int kr = k - kt;
-    for (int cw = 0; cw <= w; ++cw) {
-      const int kl = kr - cw;
-      if (kl < 0 || kl > a) continue;
-      // lo pass: it gathers the Lo/W boundary bond only, which couples the rows (T, W) and (T, W ^ 1): each pair goes to
-      // one XCD back to back, so that what one row gathers is what the other stages (their requests meet in the L2);
-      // pairs of one (cw, wr) over the T's of the class follow each other -- equal lengths side by side
-      for (int wr = 0; wr < S.nw[cw]; ++wr) {
-        const uint32_t W = ly->w_pat[S.w_off[cw] + wr];
-        const int klp = (W & 1u) ? kl + 1 : kl - 1;                 // Lo ones of the partner row (T, W ^ 1)
-        const bool partner = klp >= 0 && klp <= a;
-        if ((W & 1u) && partner) continue;                          // listed with its even partner
-        for (uint32_t T : Tby[kt]) {
-          std::vector<uint32_t> g{(T << w) | W};
-          if (partner) g.push_back((T << w) | (W ^ 1u));
-          gA.push_back(g);
-        }
-      }
-      // (real vectors: the window pass runs on pairs of entries, rows of pitch / 2 elements)
-      const int Rr = 16 << S.rs[cw], nrun = ((real ? S.pitch[kl] / 2 : S.pitch[kl]) + Rr - 1) / Rr;
-      DNM_CHECK(nrun < 4096, "internal: too many runs");
-      for (int run = 0; run < nrun; ++run) {
-        std::vector<uint32_t> g;
-        for (uint32_t T : Tby[kt]) g.push_back((T << 16) | (cw << 12) | run);
-        gB.push_back(g);
-      }
-    }
-  }
-  // Bond graphs: the lo pass gathers, for every hop between Lo and W, from the row (T, W ^ bit) -- rows that differ
-  // in the window bits such hops touch go to one XCD back to back (what one of them gathers is what another stages:
-  // the requests meet in that XCD's L2), and the groups of one window pattern over all T's follow each other, so that
-  // the partner blocks of the hops between Lo and T are at least in the Infinity Cache.  DNM_SC3G_ORDER=0: the chain's
-  // order (pairs under window bit 0).
-  if (graph && !(knob("DNM_SC3G_ORDER") && knob("DNM_SC3G_ORDER")[0] == '0')) {
-    // the bits of a row's id (T << w | W) its gathered hops flip, by the number of hops that flip them; the six most
-    // used ones span a group (DNM_SC3G_ORDER=w: window bits only, the first form of this order)
-    const bool wonly = knob("DNM_SC3G_ORDER") && knob("DNM_SC3G_ORDER")[0] == 'w';
-    std::vector<std::pair<int, int>> use;                        // (-count, bit)
-    for (int b = 0; b < t + w; ++b) {
-      int cnt = 0;
-      for (size_t q = nh[0]; q < nh[0] + nh[1]; ++q) {
-        const uint64_t fl = ((uint64_t)hops[q].mT << w) | hops[q].mW;
-        if (__builtin_popcountll(fl) == 1 && ((fl >> b) & 1ull) && !(wonly && b >= w)) ++cnt;
-      }
-      if (cnt) use.push_back({-cnt, b});
-    }
-    std::sort(use.begin(), use.end());
-    uint32_t jm = 0;
-    for (size_t q = 0; q < use.size() && q < 6; ++q) jm |= 1u << use[q].second;     // at most 64 rows to a group (what an XCD holds)
-    gA.clear();
-    std::vector<uint32_t> subs;
-    for (uint32_t sset = jm;; sset = (sset - 1) & jm) {           // the subsets of jm, descending
-      subs.push_back(sset);
-      if (!sset) break;
-    }
-    std::reverse(subs.begin(), subs.end());
-    const uint32_t wm = (1u << w) - 1u;
-    for (uint32_t W0 = 0; W0 < (1u << w); ++W0) {
-      if (W0 & jm & wm) continue;
-      for (uint32_t Tb = 0; Tb < (1u << t); ++Tb) {
-        if ((Tb << w) & jm) continue;
-        std::vector<uint32_t> g;
-        for (uint32_t sset : subs) {
-          const uint32_t id = ((Tb << w) | W0) | sset, T = id >> w, W = id & wm;
-          if (!ly->in_range(T, T0, T1)) continue;
-          const int kl = k - __builtin_popcount(T) - __builtin_popcount(W);
-          if (kl >= 0 && kl <= a) g.push_back(id);
-        }
-        if (!g.empty()) gA.push_back(g);
-      }
-    }
-  }
-  permA = pack_lo_rows(deal(gA), *ly, a == 14 ? 1024 : 256, real);       // thread counts of launch_sc3's instances
-  // Window pass: a hop between W and T (the chain's W/T boundary bond; any such pair of a bond graph) couples the class
-  // (T, cw) to (T ^ bit, cw -+ 1) at the same columns -- the same number of ones in Lo.  Workgroups of one Lo population
-  // and one block of 64 columns form a group, ordered by their first column inside it, so that such partners run on one
-  // XCD at about the same time (the first order grouped the T's of one popcount class at fixed (cw, run): partners under
-  // the hops inside T only, which this order keeps together as well).  kagome-30: the pass's fetch 59.6 -> 28.6 B/row, L2
-  // hits 49 -> 70 %, 2.40 -> 2.22 ms (profiles/r05_kagome_window_order.txt); chains: SpinConserve(32,16) 35.8 -> 30.5
-  // B/row, 5.30 -> 5.07 ms, a rank of config 5 24.6 -> 24.2 ms (profiles/r05_chain_window_order.txt).
-  // DNM_SC3G_WORDER=0: the first order.
-  const char *worder = knob("DNM_SC3G_WORDER");
-  if (!(worder && worder[0] == '0')) {
-    struct Wg { uint32_t e; int kl, col; };
-    std::vector<Wg> all;
-    for (auto &g : gB)
-      for (uint32_t e : g) {
-        const uint32_t T = e >> 16;
-        const int cw = (e >> 12) & 15, run = e & 0xfff;
-        all.push_back({e, k - __builtin_popcount(T) - cw, run * (16 << S.rs[cw])});
-      }
-    int bs = 6;                                        // log2 of the column block (2^5 ... 2^7 level, 2^8: +1.5 %, 2^10: +6 %)
-    if (const char *e = knob("DNM_SC3G_WBLOCK")) bs = atoi(e);
-    std::stable_sort(all.begin(), all.end(), [bs](const Wg &x, const Wg &y) {
-      if (x.kl != y.kl) return x.kl < y.kl;
-      if ((x.col >> bs) != (y.col >> bs)) return (x.col >> bs) < (y.col >> bs);
-      return x.col < y.col;
-    });
-    gB.clear();
-    for (size_t i = 0; i < all.size();) {
-      size_t j = i;
-      std::vector<uint32_t> g;
-      while (j < all.size() && all[j].kl == all[i].kl && (all[j].col >> bs) == (all[i].col >> bs)) g.push_back(all[j++].e);
-      gB.push_back(g);
-      i = j;
-    }
-  }
-  permB = deal(gB);
-  if (permA.empty()) permA.assign(8, 0xffffffffu);
-  if (permB.empty()) permB.assign(8, 0xffffffffu);
-  if (want_device) {
-    DNM_TRY(up(permA, &d_permA)); DNM_TRY(up(permB, &d_permB)); DNM_TRY(up(bond, &d_bond));
-    op.bond = (const double *)d_bond;
-    if (graph) {
-      DNM_TRY(up(hops, &d_hops)); DNM_TRY(up(wnb, &d_wnb));
-      const Sc3Hop *hp = (const Sc3Hop *)d_hops;
-      op.ldsA = hp; op.gatA = hp + nh[0]; op.ldsB = hp + nh[0] + nh[1]; op.gatB = hp + nh[0] + nh[1] + nh[2];
-      op.wnb = (const uint8_t *)d_wnb;
-      if (!ptab.empty()) {
-        DNM_TRY(up(ptab, &d_ptab));
-        op.ptab = (const uint16_t *)d_ptab;
-        DNM_TRY(up(pcoef, &d_pcoef));
-        op.pcoef = (const double *)d_pcoef;
-      }
-    }
-    if (diag_mode == 2) {
-      DNM_TRY(up(dlo, &d_dlo)); DNM_TRY(up(dt_sign, &d_dt_sign)); DNM_TRY(up(dt_coef, &d_dt_coef));
-      DNM_TRY(up(dt_group, &d_dt_group));
-      op.dlo = (const double *)d_dlo; op.dt_sign = (const uint64_t *)d_dt_sign;
-      op.dt_coef = (const double *)d_dt_coef; op.dt_group = (const int32_t *)d_dt_group;
-    }
-  }
-  return 0;
-}
-
-// phase 0: the whole multiply (window pass writes y, lo pass adds: one rank); phase 1: the part that needs nothing
-// from other ranks (lo pass, writes y); phase 2: the rest (window pass, adds)
-template <int A, int W, int NT, int NTW>      // NT: threads of the lo pass (512 x 7 entries: 7.4 ms against 6.4), NTW: of the window pass
+// the chain family's instances and shapes for the launcher (sc3_launch.h)
+template <int A, int W, int NTW>
 static int launch_two_pass(const Sc3Mat &M, const Sc3Call &call, const double *cached_diag, const void *xw, void *y,
                            hipStream_t st, int phase) {
-  const Sc3Tab &S = M.ly->dev;
-  // LDS: the lo pass's row; the window pass's tile plus its zero row (largest over the classes)
-  constexpr size_t ldsA = (size_t)sc3_lo_cap(A, NT) * 16;
-  size_t ldsB = 0;
-  for (int cw = 0; cw <= W; ++cw)      // ... and the class's partner table
-    ldsB = std::max(ldsB, (((size_t)M.ly->host.nw[cw] + 1) << (4 + M.ly->host.rs[cw] + 4)) + (size_t)M.ly->host.nw[cw] * 16);
-  Sc3Op op = M.op;
-  const int dm = M.diag_mode;       // 2: on the fly whether or not a cached copy exists (8 B/row less to read)
-  if (dm == 1) op.diag = cached_diag;
-  DNM_CHECK(dm != 1 || op.diag, "this operator needs its diagonal precomputed (dnm_mat_precompute_diagonal)");
-  using kern_t = void (*)(const Sc3Tab, const Sc3Op, const uint32_t *, const Sc3Call, const c128 *, c128 *);
+  constexpr int NT = sc3_lo_threads(A), NTR = sc3r_threads(NT), PPR = sc3r_pairs(A, NT);
+  Sc3LaunchShape L;
+  L.nt_lo = NT; L.nt_win = NTW; L.nt_lo_real = NTR;
+  L.lds_lo = (size_t)sc3_lo_cap(A, NT) * 16;
+  L.lds_lo_real = (size_t)sc3_lo_cap_r(A, NT) * 8;
+  for (int cw = 0; cw <= W; ++cw)      // the window pass's tile and the class's partner table
+    L.lds_win = std::max(L.lds_win, sc3_win_tile_bytes(M.ly->host, cw) + (size_t)M.ly->host.nw[cw] * 16);
   const bool lo_first = phase != 0;
-  kern_t kB = nullptr, kA = nullptr;
-  if (lo_first) kB = M.sym ? sc3_win_pass<W, NTW, true, true> : sc3_win_pass<W, NTW, false, true>;
-  else kB = M.sym ? sc3_win_pass<W, NTW, true, false> : sc3_win_pass<W, NTW, false, false>;
-#define DNM_LO(DM_, SY_) (lo_first ? (kern_t)sc3_lo_pass<A, NT, DM_, SY_, false> : (kern_t)sc3_lo_pass<A, NT, DM_, SY_, true>)
-  switch (dm * 2 + (M.sym ? 1 : 0)) {
-    case 0: kA = DNM_LO(0, false); break;
-    case 1: kA = DNM_LO(0, true); break;
-    case 2: kA = DNM_LO(1, false); break;
-    case 3: kA = DNM_LO(1, true); break;
-    case 4: kA = DNM_LO(2, false); break;
-    default: kA = DNM_LO(2, true); break;
-  }
-#undef DNM_LO
-  static std::map<const void *, bool> attr_done;
-  for (auto kp : {std::make_pair((const void *)kA, ldsA), std::make_pair((const void *)kB, ldsB)})
-    if (!attr_done[kp.first]) {
-      DNM_HIP(hipFuncSetAttribute(kp.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp.second));
-      attr_done[kp.first] = true;
-    }
-  Sc3Call first = call, second = call;
-  first.dot_out = nullptr;
-  second.zinit = nullptr;
-  second.zinit2 = nullptr;
-  if (M.real) {
-    // real vectors: the window pass is the complex kernel on the halved tables (pairs of entries as elements: every
-    // offset it forms is even), the lo pass its own kernel on doubles
-    DNM_CHECK(M.sym, "internal: real vectors need a real operator");
-    using kern_r = void (*)(const Sc3Tab, const Sc3Op, const uint32_t *, const Sc3Call, const double *, double *);
-    kern_r kR = nullptr;
-    constexpr int NTR = sc3r_threads(NT), PPR = sc3r_pairs(A, NT);
-    if (dm == 0) kR = lo_first ? (kern_r)sc3_lo_pass_r<A, NTR, PPR, 0, false> : (kern_r)sc3_lo_pass_r<A, NTR, PPR, 0, true>;
-    else if (dm == 1) kR = lo_first ? (kern_r)sc3_lo_pass_r<A, NTR, PPR, 1, false> : (kern_r)sc3_lo_pass_r<A, NTR, PPR, 1, true>;
-    else kR = lo_first ? (kern_r)sc3_lo_pass_r<A, NTR, PPR, 2, false> : (kern_r)sc3_lo_pass_r<A, NTR, PPR, 2, true>;
-    constexpr size_t ldsR = (size_t)sc3_lo_cap_r(A, NT) * 8;
-    if (!attr_done[(const void *)kR]) {
-      DNM_HIP(hipFuncSetAttribute((const void *)kR, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsR));
-      attr_done[(const void *)kR] = true;
-    }
-    Sc3Call firstw = phase == 0 ? first : second;
-    firstw.row0 /= 2;
-    firstw.win_start /= 2;
-    if (phase == 0 || phase == 2)
-      hipLaunchKernelGGL(kB, dim3((unsigned)M.permB.size()), dim3(NTW), ldsB, st, M.ly->dev_h, op, (const uint32_t *)M.d_permB,
-                         firstw, (const c128 *)xw, (c128 *)y);
-    if (phase == 0 || phase == 1)
-      hipLaunchKernelGGL(kR, dim3((unsigned)(M.permA.size() / 8)), dim3(NTR), ldsR, st, S, op, (const uint32_t *)M.d_permA,
-                         phase == 0 ? second : first, (const double *)xw, (double *)y);
-    DNM_HIP(hipGetLastError());
-    return 0;
-  }
-  if (phase == 0 || phase == 2)
-    hipLaunchKernelGGL(kB, dim3((unsigned)M.permB.size()), dim3(NTW), ldsB, st, S, op, (const uint32_t *)M.d_permB,
-                       phase == 0 ? first : second, (const c128 *)xw, (c128 *)y);
-  if (phase == 0 || phase == 1)
-    hipLaunchKernelGGL(kA, dim3((unsigned)(M.permA.size() / 8)), dim3(NT), ldsA, st, S, op, (const uint32_t *)M.d_permA,
-                       phase == 0 ? second : first, (const c128 *)xw, (c128 *)y);
-  DNM_HIP(hipGetLastError());
-  return 0;
+  Sc3Kernels K;
+  if (lo_first) K.win = M.sym ? sc3_win_pass<W, NTW, true, true> : sc3_win_pass<W, NTW, false, true>;
+  else K.win = M.sym ? sc3_win_pass<W, NTW, true, false> : sc3_win_pass<W, NTW, false, false>;
+  K.win_real = K.win;
+  K.lo = DNM_SC3_PICK_LO(sc3_lo_pass, A, NT, M.diag_mode, M.sym, lo_first);
+  K.lo_real = DNM_SC3_PICK_LO_REAL(sc3_lo_pass_r, A, NTR, PPR, M.diag_mode, lo_first);
+  return sc3_launch_passes(M, K, L, call, cached_diag, xw, y, st, phase);
 }
-
-size_t sc3_dot_partials(const Sc3Mat &M) { return M.permA.size() / 8; }
 
 int launch_sc3(const Sc3Mat &M, const DevMsc &msc, const Sc3Call &call, const double *cached_diag, const void *xw,
                void *y, hipStream_t st, int phase) {
@@ -1939,17 +1122,15 @@ int launch_sc3(const Sc3Mat &M, const DevMsc &msc, const Sc3Call &call, const do
     if (M.graph) return launch_sc3g(M, call, cached_diag, xw, y, st, phase);
     if (M.ly->host.a == 14) {
       static const bool w1024 = [] { const char *e = knob("DNM_SC3_WIN_THREADS"); return e && atoi(e) == 1024; }();   // experiments
-      if (w1024) return launch_two_pass<14, 10, 1024, 1024>(M, call, cached_diag, xw, y, st, phase);
-      return launch_two_pass<14, 10, 1024, 512>(M, call, cached_diag, xw, y, st, phase);
+      if (w1024) return launch_two_pass<14, 10, 1024>(M, call, cached_diag, xw, y, st, phase);
+      return launch_two_pass<14, 10, sc3_win_threads(14)>(M, call, cached_diag, xw, y, st, phase);
     }
-    // (256 threads for rows of at most 20 states: the small instance runs four rows per workgroup, so that the tests
-    // at L = 11...24 cover the sub-group form of the lo pass)
-    return launch_two_pass<6, 4, 256, 64>(M, call, cached_diag, xw, y, st, phase);
+    return launch_two_pass<6, 4, sc3_win_threads(6)>(M, call, cached_diag, xw, y, st, phase);
   }
   DNM_CHECK(!call.dot_out, "internal: the row kernel has no fused sums");
   if (M.rowsel.empty()) return 0;      // a rank that owns no rows
   hipLaunchKernelGGL(sc3_row_kernel, dim3((unsigned)M.rowsel.size()), dim3(SC3_ROW_NT), 0, st, M.ly->dev, msc,
-                     (const uint32_t *)M.d_rowsel, call, cached_diag, (const c128 *)xw, (c128 *)y);
+                     M.d_rowsel.as<uint32_t>(), call, cached_diag, (const c128 *)xw, (c128 *)y);
   DNM_HIP(hipGetLastError());
   return 0;
 }

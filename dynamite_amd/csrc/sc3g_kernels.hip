@@ -17,11 +17,11 @@
 #include "sc3.h"
 
 #include <algorithm>
-#include <map>
 
 #include "dnm_common.h"
 #include "kernels.h"
 #include "sc3_dev.h"
+#include "sc3_launch.h"
 
 #ifndef DNM_SC3G_PROBE_STAGE
 #define DNM_SC3G_PROBE_STAGE 0
@@ -942,92 +942,33 @@ sc3g_win_pass(const Sc3Tab S, const Sc3Op O, const uint32_t *__restrict__ perm, 
 
 }  // namespace
 
-// phase 0: window pass writes y, lo pass adds (one rank); phase 1: lo pass alone (writes y); phase 2: window pass (adds)
-template <int A, int W, int NT, int NTW>
+// the bond-graph family's instances and shapes for the launcher (sc3_launch.h)
+template <int A, int W>
 static int launch_graph_passes(const Sc3Mat &M, const Sc3Call &call, const double *cached_diag, const void *xw, void *y,
                                hipStream_t st, int phase) {
-  const Sc3Tab &S = M.ly->dev;
-  constexpr size_t ldsA = (size_t)sc3_lo_cap(A, NT) * 16;
-  size_t ldsB = 0;
-  for (int cw = 0; cw <= W; ++cw)
-    ldsB = std::max(ldsB, (((size_t)M.ly->host.nw[cw] + 1) << (4 + M.ly->host.rs[cw] + 4)) +
-                              (((size_t)M.ly->host.nw[cw] * (size_t)M.op.nldsB + 15) & ~(size_t)15));
-  Sc3Op op = M.op;
-  const int dm = M.diag_mode;
-  if (dm == 1) op.diag = cached_diag;
-  DNM_CHECK(dm != 1 || op.diag, "this operator needs its diagonal precomputed (dnm_mat_precompute_diagonal)");
-  using kern_t = void (*)(const Sc3Tab, const Sc3Op, const uint32_t *, const Sc3Call, const c128 *, c128 *);
+  constexpr int NT = sc3_lo_threads(A), NTW = sc3_win_threads(A), NTR = sc3r_threads(NT), PPR = sc3r_pairs(A, NT);
+  Sc3LaunchShape L;
+  L.nt_lo = NT; L.nt_win = NTW; L.nt_lo_real = NTR;
+  L.lds_lo = (size_t)sc3_lo_cap(A, NT) * 16;
+  L.lds_lo_real = (size_t)sc3_lo_cap_r(A, NT) * 8;
+  for (int cw = 0; cw <= W; ++cw)      // the window pass's tile and the class's partner rows (Sc3Op::wnb)
+    L.lds_win = std::max(L.lds_win, sc3_win_tile_bytes(M.ly->host, cw) +
+                                        (((size_t)M.ly->host.nw[cw] * (size_t)M.op.nldsB + 15) & ~(size_t)15));
   const bool lo_first = phase != 0;
-  kern_t kB = nullptr, kA = nullptr;
-  if (lo_first) kB = M.sym ? sc3g_win_pass<W, NTW, true, true> : sc3g_win_pass<W, NTW, false, true>;
-  else kB = M.sym ? sc3g_win_pass<W, NTW, true, false> : sc3g_win_pass<W, NTW, false, false>;
-#define DNM_LO(DM_, SY_) (lo_first ? (kern_t)sc3g_lo_pass<A, NT, DM_, SY_, false> : (kern_t)sc3g_lo_pass<A, NT, DM_, SY_, true>)
-  switch (dm * 2 + (M.sym ? 1 : 0)) {
-    case 0: kA = DNM_LO(0, false); break;
-    case 1: kA = DNM_LO(0, true); break;
-    case 2: kA = DNM_LO(1, false); break;
-    case 3: kA = DNM_LO(1, true); break;
-    case 4: kA = DNM_LO(2, false); break;
-    default: kA = DNM_LO(2, true); break;
-  }
-#undef DNM_LO
-  static std::map<const void *, size_t> attr_done;
-  for (auto kp : {std::make_pair((const void *)kA, ldsA), std::make_pair((const void *)kB, ldsB)})
-    if (attr_done[kp.first] < kp.second) {
-      DNM_HIP(hipFuncSetAttribute(kp.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp.second));
-      attr_done[kp.first] = kp.second;
-    }
-  Sc3Call first = call, second = call;
-  first.dot_out = nullptr;
-  second.zinit = nullptr;
-  second.zinit2 = nullptr;
-  if (M.real) {
-    // real vectors: the window pass is the complex kernel on the halved tables (pairs of entries as elements; its REALV
-    // instance takes the pairs apart where XParity's flip-composed hops read columns backwards), the lo pass its own
-    // kernel on doubles
-    DNM_CHECK(M.sym, "internal: real vectors need a real operator");
-    using kern_r = void (*)(const Sc3Tab, const Sc3Op, const uint32_t *, const Sc3Call, const double *, double *);
-    kern_r kR = nullptr;
-    constexpr int NTR = sc3r_threads(NT), PPR = sc3r_pairs(A, NT);
-#define DNM_LOR(DM_) (lo_first ? (kern_r)sc3g_lo_pass_r<A, NTR, PPR, DM_, false> : (kern_r)sc3g_lo_pass_r<A, NTR, PPR, DM_, true>)
-    kR = dm == 0 ? DNM_LOR(0) : (dm == 1 ? DNM_LOR(1) : DNM_LOR(2));
-#undef DNM_LOR
-    constexpr size_t ldsR = (size_t)sc3_lo_cap_r(A, NT) * 8;
-    if (attr_done[(const void *)kR] < ldsR) {
-      DNM_HIP(hipFuncSetAttribute((const void *)kR, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsR));
-      attr_done[(const void *)kR] = ldsR;
-    }
-    Sc3Call firstw = phase == 0 ? first : second;
-    firstw.row0 /= 2;
-    firstw.win_start /= 2;
-    kern_t kBr = lo_first ? (kern_t)sc3g_win_pass<W, NTW, true, true, true> : (kern_t)sc3g_win_pass<W, NTW, true, false, true>;
-    if (attr_done[(const void *)kBr] < ldsB) {
-      DNM_HIP(hipFuncSetAttribute((const void *)kBr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB));
-      attr_done[(const void *)kBr] = ldsB;
-    }
-    if (phase == 0 || phase == 2)
-      hipLaunchKernelGGL(kBr, dim3((unsigned)M.permB.size()), dim3(NTW), ldsB, st, M.ly->dev_h, op, (const uint32_t *)M.d_permB,
-                         firstw, (const c128 *)xw, (c128 *)y);
-    if (phase == 0 || phase == 1)
-      hipLaunchKernelGGL(kR, dim3((unsigned)(M.permA.size() / 8)), dim3(NTR), ldsR, st, S, op, (const uint32_t *)M.d_permA,
-                         phase == 0 ? second : first, (const double *)xw, (double *)y);
-    DNM_HIP(hipGetLastError());
-    return 0;
-  }
-  if (phase == 0 || phase == 2)
-    hipLaunchKernelGGL(kB, dim3((unsigned)M.permB.size()), dim3(NTW), ldsB, st, S, op, (const uint32_t *)M.d_permB,
-                       phase == 0 ? first : second, (const c128 *)xw, (c128 *)y);
-  if (phase == 0 || phase == 1)
-    hipLaunchKernelGGL(kA, dim3((unsigned)(M.permA.size() / 8)), dim3(NT), ldsA, st, S, op, (const uint32_t *)M.d_permA,
-                       phase == 0 ? second : first, (const c128 *)xw, (c128 *)y);
-  DNM_HIP(hipGetLastError());
-  return 0;
+  Sc3Kernels K;
+  if (lo_first) K.win = M.sym ? sc3g_win_pass<W, NTW, true, true> : sc3g_win_pass<W, NTW, false, true>;
+  else K.win = M.sym ? sc3g_win_pass<W, NTW, true, false> : sc3g_win_pass<W, NTW, false, false>;
+  K.lo = DNM_SC3_PICK_LO(sc3g_lo_pass, A, NT, M.diag_mode, M.sym, lo_first);
+  K.lo_real = DNM_SC3_PICK_LO_REAL(sc3g_lo_pass_r, A, NTR, PPR, M.diag_mode, lo_first);
+  // (real vectors: the REALV instance takes the pairs apart where XParity's flip-composed hops read columns backwards)
+  K.win_real = lo_first ? (sc3_kern_t)sc3g_win_pass<W, NTW, true, true, true> : (sc3_kern_t)sc3g_win_pass<W, NTW, true, false, true>;
+  return sc3_launch_passes(M, K, L, call, cached_diag, xw, y, st, phase);
 }
 
 int launch_sc3g(const Sc3Mat &M, const Sc3Call &call, const double *cached_diag, const void *xw, void *y, hipStream_t st,
                 int phase) {
-  if (M.ly->host.a == 14) return launch_graph_passes<14, 10, 1024, 512>(M, call, cached_diag, xw, y, st, phase);
-  return launch_graph_passes<6, 4, 256, 64>(M, call, cached_diag, xw, y, st, phase);
+  if (M.ly->host.a == 14) return launch_graph_passes<14, 10>(M, call, cached_diag, xw, y, st, phase);
+  return launch_graph_passes<6, 4>(M, call, cached_diag, xw, y, st, phase);
 }
 
 }  // namespace dnm

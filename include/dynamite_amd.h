@@ -256,6 +256,14 @@ int dnm_mat_export_diag_tables(const dnm_mat *A, int remote, int idx, double *db
                                int64_t *ndblock, double *dtile_out, int64_t max_dtile, int64_t *ndtile,
                                uint64_t *masks_out, int *nmasks);
 
+/* One host table of the SpinConserve passes of a handle whose vectors are in the internal layout (an error on any other
+ * handle; host-only handles have them too), by name: rowsel needT hops wnb ptab pcoef permA permB bond dlo dt_sign
+ * dt_coef dt_group -- the bytes the device gets (hops: 64-byte records mT mW mLo half dfield dbit pad pad as int32, then
+ * up_re up_im dn_re dn_im).  "op": uint64 present, bondsA, bondsB, then int32 ndt, ngroups, glo[4], nldsA, ngatA, nldsB,
+ * ngatB, nhp, ptab_row[18], tiled, graph, sym, real, diag_mode (160 bytes).  *nbytes: the table's size; null out: the
+ * size alone */
+int dnm_mat_export_sc3(const dnm_mat *A, const char *name, void *out, size_t max_bytes, size_t *nbytes);
+
 /* --- partitioned multiply: replaces the VecScatterCreateToAll all-gather of
  * bcuda_template_2.cu:161-171 with an XOR-partner exchange. ---------------- */
 /* One block transfer of the exchange: `count` amplitudes starting at `offset`

@@ -20,7 +20,6 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 void DevBuf::release() {}
-Sc3Mat::~Sc3Mat() {}
 bool tile_config_supported(int B, int logR) { return (B == 8 && logR == 2) || (B == 10 && (logR == 2 || logR == 3)); }
 }  // namespace dnm
 dnm_mat::~dnm_mat() {}

@@ -408,6 +408,75 @@ def test_xparity_production_instance():
     H.destroy_mat()
 
 
+# ---- the branches of the shared launcher (csrc/sc3_launch.h) no other test reaches ----------------------------
+
+def _hopping_only(L, graph, complex_hops):
+    """XX + YY (optionally plus XY - YX) on a chain or on a chain with a few long bonds, and nothing else: an operator
+    without a diagonal, so that the passes run in their DIAGM 0 instances."""
+    from dynamite_amd.operators import sigmax, sigmay, op_sum
+    pairs = [(i, i + 1) for i in range(L - 1)] + ([(0, 5), (2, 8), (1, 11), (3, 9)] if graph else [])
+    rs = np.random.RandomState(17)
+    terms = []
+    for i, j in pairs:
+        terms.append(rs.uniform(0.2, 1) * (sigmax(i) * sigmax(j) + sigmay(i) * sigmay(j)))
+        if complex_hops:
+            terms.append(rs.uniform(0.2, 1) * (sigmax(i) * sigmay(j) - sigmay(i) * sigmax(j)))
+    H = op_sum(terms)
+    H.L = L
+    return H
+
+
+@pytest.mark.parametrize("family,diag,arith", [("chain", "none", "complex"), ("chain", "none", "complex_hops"),
+                                               ("chain", "none", "real"), ("graph", "none", "complex"),
+                                               ("graph", "none", "complex_hops"), ("graph", "none", "real"),
+                                               ("graph", "cached", "real")])
+def test_launcher_branches(small_layout, monkeypatch, family, diag, arith):
+    """L = 12, k = 6 in the (6, 4) layout, against the oracle: both kernel families without a diagonal (symmetric and
+    direction-dependent hops, complex and real vectors), and the bond-graph passes on real vectors with the cached
+    diagonal (DNM_SC3_DIAG=cached).  Bar: 8 nnz eps max|c| max|x|, nnz = the masks of the operator (the most entries a
+    row has)."""
+    import ctypes as C
+    import torch
+    from dynamite_amd import _lib
+    from gpu_util import vec_for
+    L, k = 12, 6
+    if diag == "none":
+        H = _hopping_only(L, family == "graph", arith == "complex_hops")
+    else:
+        H = pair_graph(L, seed=3, nbonds=20, fields=True)
+        monkeypatch.setenv("DNM_SC3_DIAG", "cached")
+    sub = SpinConserve(L, k)
+    n = sub.get_dimension()
+    assert n == 924
+    mat = shell(H, sub, flags=_lib.MAT_REAL_PACKED if arith == "real" else 0, site_perm=False)
+    d = mat.describe()
+    assert ("bond graph" in d) == (family == "graph") and "two-pass" in d, d
+    assert ("diagonal none" in d) == (diag == "none") and ("diagonal cached" in d) == (diag == "cached"), d
+    assert ("real symmetric" in d) == (arith != "complex_hops"), d
+    if mat.uses_cached_diagonal():
+        mat.precompute_diagonal()
+    x = rand_state(n, seed=9)
+    if arith == "real":
+        x = x.real + 0j
+    want = orc.matvec(orc_msc(H), orc_sub(sub), orc_sub(sub), x)
+    tol = 8 * len(set(H.msc['masks'].tolist())) * 2.2e-16 * np.abs(H.msc['coeffs']).max() * np.abs(x).max()
+    if arith == "real":
+        v = vec_for(sub)
+        v.set_local_from_numpy(x)
+        xd = v.array.real.contiguous()
+        yd = torch.full_like(xd, 7.0)
+        _lib.check(_lib.lib().dnm_mat_mult(mat.handle, C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()), None))
+        out = vec_for(sub)
+        _lib.check(_lib.lib().dnm_vec_layout_unpack_real(C.byref(sub._c()), None, out.ptr, C.c_void_p(yd.data_ptr()), None))
+        got = out.local_numpy()
+        assert np.abs(got.imag).max() == 0.0 and np.abs(want.imag).max() == 0.0
+    else:
+        got = mult_numpy(mat, x)
+    print("max error %.3e, bar %.3e" % (np.abs(got - want).max(), tol))
+    assert np.abs(got - want).max() <= tol, d
+    mat.destroy()
+
+
 # ---- real arithmetic ---------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", ["kagome15", "graph13", "graph14_fields"])
