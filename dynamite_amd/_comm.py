@@ -128,5 +128,18 @@ def reduce_sum(tensor, dst=0):
         dist.reduce(flat, dst=dst)
 
 
+def all_reduce_sum_host(arr):
+    """A host array of float64 summed over the ranks; every rank gets the sum (a new numpy array of the same shape).
+    gloo reduces host memory as it is; RCCL needs it on the rank's device."""
+    import numpy as np
+    t = torch.from_numpy(np.array(arr, dtype=np.float64))
+    if dist.get_backend() == 'gloo':
+        dist.all_reduce(t)
+        return t.numpy()
+    t = t.cuda()
+    dist.all_reduce(t)
+    return t.cpu().numpy()
+
+
 def barrier():
     dist.barrier()

@@ -1775,6 +1775,48 @@ def rdm_sector_blocks(vec, subspace, keep, xparity_sector, sectors, plan=None, w
     return out
 
 
+def zz_moments_plan(sub_c, nrows):
+    """``dnm_zz_moments_plan`` (host only): (tile rows of 16, workgroups, bytes of their partial tiles) of the sweep
+    over ``nrows`` rows of the subspace."""
+    tr, nw, sb = C.c_int(), C.c_int(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_zz_moments_plan(C.byref(sub_c), int(nrows), C.byref(tr), C.byref(nw), C.byref(sb)))
+    return tr.value, nw.value, int(sb.value)
+
+
+def zz_moments_block(x_block, sub_c, row0, nrows):
+    """``dnm_zz_moments`` of one block: host array (L + 1, L + 1) float64, the raw sums over the ``nrows`` amplitudes
+    of the rows [row0, row0 + nrows) that the device tensor ``x_block`` holds."""
+    D = int(sub_c.L) + 1
+    out = np.empty((D, D), dtype=np.float64)
+    _lib.check(_lib.lib().dnm_zz_moments(C.c_void_p(x_block.data_ptr()), C.byref(sub_c), int(row0), int(nrows),
+                                         _lib.pf64(out), _stream()))
+    return out
+
+
+def zz_moments(vec, subspace):
+    """All first and second sigma-z moments of the state in ``vec`` in one pass: numpy array M of shape
+    (L + 1, L + 1) with M[0, 0] = <psi|psi>, M[0, 1 + i] = <sigmaz_i>, M[1 + i, 1 + j] = <sigmaz_i sigmaz_j> (raw sums,
+    nothing normalised; sign +1 for a clear bit).  ``subspace`` is the descriptor of the product-state subspace whose
+    rows [vec.start, vec.start + vec.rows) the vector holds -- for an XParity vector its parent's, the sum then runs
+    over the representatives.  Swizzled Full / Parity vectors are read as they lie (at L = 30 there is no room for a
+    copy).  A SpinConserve vector in the internal layout is converted to reference order first, as for the reduced
+    density matrix: that costs one extra vector.  On several ranks each rank sweeps its block and the (L + 1)^2 sums
+    are added over the ranks; every rank gets the result."""
+    config._initialize()
+    sub_c = subspace['data']
+    x = vec.array
+    if vec.internal:
+        x = vec.local_natural()
+        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
+        sub_c.vec_swizzle = 0
+        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    M = zz_moments_block(x, sub_c, vec.start, vec.rows)
+    if _dist() is not None:
+        from . import _comm
+        M = _comm.all_reduce_sum_host(M)
+    return M
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -635,6 +635,34 @@ def entanglement_spectrum(state, keep):
     return _rdm_spectrum(state, keep)
 
 
+def sigmaz_correlations(state, connected=False):
+    """Every local magnetisation and every two-site sigma-z correlator of ``state`` from one pass over it (one
+    matrix-core kernel, ``backend.zz_moments``) instead of L (L + 1) / 2 calls of ``Operator.expectation``, each a
+    multiply and a temporary vector.  Returns ``(mz, zz)``, float64: ``mz[i]`` = <psi|sigmaz_i|psi> and ``zz[i, j]`` =
+    <psi|sigmaz_i sigmaz_j|psi>, with the sign ``sigmaz(i).expectation`` gives and nothing normalised, as
+    ``expectation`` normalises nothing; ``zz`` is symmetric and its diagonal is <psi|psi>.  ``connected``: ``zz`` is
+    ``zz / n - outer(mz, mz) / n**2`` with n = <psi|psi>, the connected correlator of the normalised state.
+
+    States on XParity subspaces: sigmaz_i sigmaz_j commutes with the global flip, so ``zz`` is the same sum over the
+    representatives, and every <sigmaz_i> vanishes by symmetry -- ``mz`` is exact zeros.  Every process gets the result."""
+    from . import backend
+    from .subspaces import XParity
+    state.assert_initialized()
+    config._initialize()
+    sp = state.subspace
+    flip_sector = type(sp) is XParity
+    if not (sp.product_state_basis or flip_sector):
+        raise ValueError('sigma-z correlations need a product state basis or an XParity subspace, not %r' % (sp,))
+    # (an XParity descriptor is its parent's: the vector holds the parent's first dim / 2 rows)
+    M = backend.zz_moments(state.vec, sp._to_c())
+    mz = np.zeros(M.shape[0] - 1) if flip_sector else M[0, 1:].copy()
+    zz = M[1:, 1:].copy()
+    if connected:
+        n = M[0, 0]
+        zz = zz / n - np.outer(mz, mz) / n ** 2
+    return mz, zz
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

@@ -152,6 +152,15 @@ int launch_rdm_sector(const void *x, const SubView &sub, const RdmGeom &geo, boo
                       int nblocks, const RdmSectorBlock *blocks, int64_t ntiles, int nsplit, size_t table_bytes,
                       void *scratch, hipStream_t st);
 
+// First and second sigma-z moments of a state (zz_kernels.hip).  zz_plan is host arithmetic: tile rows of 16 of the
+// (L + 1) x (L + 1) result, the workgroups and the positions each sweeps -- functions of nrows alone -- and the bytes
+// of their partial tiles.  launch_zz_moments: x = the nrows amplitudes of rows [row0, row0 + nrows) of `sub` (device
+// view; swizzled Full / Parity layouts act on the local position), partial = scratch of the plan's size, out =
+// (L + 1)^2 doubles on the device.
+void zz_plan(int L, int64_t nrows, int *tile_rows, int *nworkgroups, int64_t *per_wg, size_t *scratch_bytes);
+int launch_zz_moments(const void *x, const SubView &sub, int64_t row0, int64_t nrows, void *partial, double *out,
+                      hipStream_t st);
+
 // ---- vector kernels ---------------------------------------------------------
 int vk_set(void *x, int64_t n, double re, double im, hipStream_t st);
 int vk_copy(void *y, const void *x, int64_t n, hipStream_t st);      // y = x (complex128 elements; no overlap)

@@ -484,6 +484,60 @@ int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size,
   return 0;
 }
 
+// ---- first and second sigma-z moments -----------------------------------------------------------------------------
+// what the plan and the call check alike: the descriptor, the layout and the rows
+static int zz_check(const dnm_subspace *sub, int64_t row0, int64_t nrows, SubView *v) {
+  DNM_CHECK(sub, "null argument");
+  DNM_TRY(view_from_c(sub, v));
+  DNM_CHECK(v->sc3 == 0, "sigma-z moments read a SpinConserve state in reference order (vec_swizzle %d given: "
+            "dnm_vec_layout_copy converts)", v->sc3);
+  DNM_CHECK(sub->site_perm == nullptr, "sigma-z moments take no relabelled subspace (site_perm given): hand over the "
+            "state in reference order with a descriptor without it");
+  const int64_t dim = sub_dim(*v);
+  DNM_CHECK(nrows >= 0 && row0 >= 0 && nrows <= dim && row0 <= dim - nrows,
+            "rows [%lld, %lld + %lld) of a subspace of dimension %lld", (long long)row0, (long long)row0,
+            (long long)nrows, (long long)dim);
+  const int64_t run = (int64_t)1 << v->swz;
+  DNM_CHECK(v->swz == 0 || nrows <= run || nrows % run == 0, "a block of %lld rows has no layout of swizzle shift %d: "
+            "beyond 2^%d rows the size must be a multiple of 2^%d", (long long)nrows, v->swz, v->swz, v->swz);
+  return 0;
+}
+
+int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
+                        size_t *scratch_bytes) {
+  SubView v{};
+  DNM_TRY(zz_check(sub, 0, nrows, &v));
+  int nb, nwg;
+  int64_t per_wg;
+  size_t bytes;
+  zz_plan(v.L, nrows, &nb, &nwg, &per_wg, &bytes);
+  if (tile_rows) *tile_rows = nb;
+  if (nworkgroups) *nworkgroups = nwg;
+  if (scratch_bytes) *scratch_bytes = bytes;
+  return 0;
+}
+
+int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream) {
+  DNM_CHECK(out && (x || nrows == 0), "null argument");
+  SubView v{};
+  DNM_TRY(zz_check(sub, row0, nrows, &v));
+  int nb, nwg;
+  int64_t per_wg;
+  size_t pbytes;
+  zz_plan(v.L, nrows, &nb, &nwg, &per_wg, &pbytes);
+  const size_t D = (size_t)v.L + 1;
+  SubOwned s;
+  DNM_TRY(s.init(sub, true));
+  DevBuf big;
+  void *scratch = nullptr;       // the partial tiles, then the matrix
+  DNM_TRY(rdm_scratch(pbytes + D * D * sizeof(double), &big, &scratch, "sigma-z moments", (long long)(nb * (nb + 1) / 2),
+                      16, nwg));
+  double *m_dev = (double *)((char *)scratch + pbytes);
+  DNM_TRY(launch_zz_moments(x, s.dev, row0, nrows, scratch, m_dev, S(stream)));
+  // (synchronises: the subspace tables are released on return)
+  return dnm_memcpy_d2h(out, m_dev, D * D * sizeof(double), stream);
+}
+
 // ---- shell matrix -------------------------------------------------------------
 // Decide whether the SpinConserve block kernel runs and build its table.  DNM_SC_BLOCK = 0 (row kernel),
 // 10 / 13 (low bits per block); default: 13 when the blocks are large enough to fill a workgroup.

@@ -259,6 +259,11 @@ class State:
         from . import computations
         return computations.entanglement_entropy(self, keep)
 
+    def sigmaz_correlations(self, connected=False):
+        """``(mz, zz)``: every <sigmaz_i> and <sigmaz_i sigmaz_j> in one pass -> computations.sigmaz_correlations."""
+        from . import computations
+        return computations.sigmaz_correlations(self, connected=connected)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

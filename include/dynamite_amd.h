@@ -195,6 +195,25 @@ int dnm_rdm_sector_plan(const dnm_subspace *sub, int keep_size, const int64_t *k
                         size_t *scratch_bytes_max);
 int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
                           int xparity_sector, int nsel, const int32_t *sel_n, void *const *out_ptrs, void *stream);
+/* Every <sigmaz_i> and <sigmaz_i sigmaz_j> of a state in one pass over it (no counterpart in the reference, whose users
+ * call Operator.expectation once per site and per pair: one multiply and one temporary vector each).  With s_i(c) = +1
+ * where bit i of the configuration c is clear and -1 where it is set, and s~(c) = (1, s_0, ..., s_{L-1}),
+ *   M = sum_c |x_c|^2 s~(c) s~(c)^T      ((L + 1) x (L + 1) doubles, row-major, real symmetric):
+ * M[0][0] = <x|x>, M[0][1+i] = <sigmaz_i>, M[1+i][1+j] = <sigmaz_i sigmaz_j>.  Sums are raw (nothing is normalised);
+ * M is symmetric to the last bit, every diagonal entry equals M[0][0], and two calls return the same bits on any device.
+ * x (device) holds the nrows amplitudes of the rows [row0, row0 + nrows) of sub, so that blocks of a partitioned state
+ * and the XParity half of a state (the parent's descriptor, nrows = dim / 2: sigmaz_i sigmaz_j commutes with the global
+ * flip, the sum over the representatives is <sigmaz_i sigmaz_j>) are summed by the caller.  Layout of x: vec_swizzle 0
+ * is index order; the XOR swizzle of Full / Parity is read as it lies and acts on the block's own positions (nrows <=
+ * 2^S or a multiple of 2^S, as for dnm_vec_swizzle_copy); the SpinConserve internal layout and a non-null site_perm are
+ * refused -- the caller converts (dnm_vec_layout_copy).  L <= 63.  out: HOST, (L + 1)^2 doubles; the call synchronises
+ * the stream like dnm_vec_dot.
+ * dnm_zz_moments_plan (host only, no device needed): tile_rows = ceil((L + 1) / 16) rows of 16 x 16 tiles, the
+ * workgroups of the sweep -- a function of nrows alone, never of the device -- and the bytes of their partial tiles,
+ * nworkgroups * tile_rows (tile_rows + 1) / 2 * 256 * 8; any output may be null. */
+int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
+                        size_t *scratch_bytes);
+int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
