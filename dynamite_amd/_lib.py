@@ -132,6 +132,10 @@ SIGNATURES = {
     "dnm_zz_moments_plan": (C.c_int, [C.POINTER(Subspace), C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_size_t)]),
     "dnm_zz_moments": (C.c_int, [vp, C.POINTER(Subspace), C.c_int64, C.c_int64, f64p, vp]),
+    "dnm_pm_moments_plan": (C.c_int, [C.POINTER(Subspace), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "dnm_pm_moments": (C.c_int, [vp, C.POINTER(Subspace), f64p, vp]),
+    "dnm_pm_partner_indices": (C.c_int, [C.POINTER(Subspace), C.c_int64, i64p, i64p]),
     "dnm_vec_set_random_swz": (C.c_int, [vp, C.c_int64, C.c_uint64, C.c_int64, C.c_int, vp]),
     "dnm_vec_swizzle_copy": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp]),
     "dnm_vec_unpack_real": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp]),

@@ -1817,6 +1817,55 @@ def zz_moments(vec, subspace):
     return M
 
 
+def pm_moments_plan(sub_c):
+    """``dnm_pm_moments_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
+    launch, bytes of the partial tiles) of the sigma+ sigma- sweep over a state of the subspace."""
+    tr, pb, nw, lb, sb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_pm_moments_plan(C.byref(sub_c), C.byref(tr), C.byref(pb), C.byref(nw), C.byref(lb),
+                                              C.byref(sb)))
+    return tr.value, pb.value, nw.value, int(lb.value), int(sb.value)
+
+
+def pm_partner_indices(sub_c, rows):
+    """``dnm_pm_partner_indices`` (host only, SpinConserve(L, k)): int64 array (len(rows), L) -- for the row of index
+    ``rows[n]`` in the sector with k + 1 set bits, the index in sector k of that configuration with bit j cleared, -1
+    where bit j is clear."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    out = np.empty((rows.size, int(sub_c.L)), dtype=np.int64)
+    _lib.check(_lib.lib().dnm_pm_partner_indices(C.byref(sub_c), rows.size, _lib.p64(rows), _lib.p64(out)))
+    return out
+
+
+def pm_moments(vec, subspace):
+    """The raw sigma+ sigma- moments of the state in ``vec`` in one pass: numpy array P of shape (L, L), complex128,
+    P[i, j] = sum_r conj(A[r, i]) A[r, j] with A[r, j] = psi(r ^ e_j) on the configurations r whose bit j is set, so that
+    <psi|sigma_plus(i) sigma_minus(j)|psi> = 4 P[i, j] (raw sums, nothing normalised; P is Hermitian to the last bit).
+    ``subspace`` is the descriptor of the Full, Parity or SpinConserve subspace of the vector.  Swizzled Full / Parity
+    vectors are read as they lie; a SpinConserve vector in the internal layout is converted to reference order first
+    (one extra vector).  The partners of a rank's rows lie on other ranks: on more than one rank this raises
+    ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('sigma+ sigma- moments of a partitioned state: the partner amplitudes of a rank\'s '
+                                  'rows lie on other ranks')
+    sub_c = subspace['data']
+    x = vec.array
+    if vec.internal:
+        x = vec.local_natural()
+        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
+        sub_c.vec_swizzle = 0
+        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    L = int(sub_c.L)
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
+    if x.numel() != full.value:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), full.value))
+    out = np.empty((L, L), dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_pm_moments(C.c_void_p(x.data_ptr()), C.byref(sub_c),
+                                         out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return out
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -663,6 +663,48 @@ def sigmaz_correlations(state, connected=False):
     return mz, zz
 
 
+def _pm_subspace(state, what):
+    from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
+    sp = state.subspace
+    if type(sp) is XParity:
+        raise ValueError('%s of an XParity state: sigma+_i sigma-_j does not commute with the global spin flip, so the '
+                         'sum over the representatives is not the expectation value (expand the state first)' % what)
+    if isinstance(sp, Explicit) or not isinstance(sp, (Full, Parity, SpinConserve)):
+        raise ValueError('%s need a Full, Parity or SpinConserve subspace, not %r' % (what, sp))
+    return sp
+
+
+def sigma_pm_correlations(state):
+    """Every <psi|sigma_plus(i) sigma_minus(j)|psi> of ``state`` from one pass over it (one matrix-core kernel,
+    ``backend.pm_moments``) instead of L (L - 1) calls of ``Operator.expectation``, each a multiply and a temporary
+    vector.  Returns ``pm``, complex128 of shape (L, L): ``pm[i, j]`` = <psi|sigma_plus(i) sigma_minus(j)|psi> with
+    sigma_plus = sigmax + i sigmay without a factor 1/2 and nothing normalised, as ``expectation`` normalises nothing.
+    ``Operator.expectation`` builds Hermitian operators only; in its terms ``pm.real[i, j]`` is
+    ``(sigmax(i) * sigmax(j) + sigmay(i) * sigmay(j)).expectation(state)`` -- <sigmax_i sigmax_j + sigmay_i sigmay_j>
+    for i != j -- and ``pm.imag[i, j]`` is ``(sigmay(i) * sigmax(j) - sigmax(i) * sigmay(j)).expectation(state)``.
+    ``pm`` is Hermitian to the last bit and its diagonal is that of sigma_plus(i) sigma_minus(i) = 2 (1 + sigmaz_i),
+    from the same sums ``sigmaz_correlations`` returns.
+
+    Full, Parity and SpinConserve states on one process.  XParity states are refused: sigma+_i sigma-_j does not
+    commute with the global flip, the sum over the representatives is not the answer."""
+    from . import backend
+    state.assert_initialized()
+    config._initialize()
+    sp = _pm_subspace(state, 'sigma+ sigma- correlations')
+    return 4.0 * backend.pm_moments(state.vec, sp._to_c())
+
+
+def spin_correlations(state):
+    """``ss[i, j]`` = <psi|sigma_i . sigma_j|psi> = <sigmax_i sigmax_j + sigmay_i sigmay_j + sigmaz_i sigmaz_j>, float64
+    of shape (L, L), nothing normalised: ``zz[i, j] + pm[i, j].real`` off the diagonal (``sigmaz_correlations`` and
+    ``sigma_pm_correlations``: two passes over the state) and 3 <psi|psi> on it."""
+    _pm_subspace(state, 'spin correlations')
+    _, zz = sigmaz_correlations(state)
+    ss = zz + sigma_pm_correlations(state).real
+    np.fill_diagonal(ss, 3.0 * np.diag(zz))
+    return ss
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

@@ -2,6 +2,7 @@
 // norm / diagonal / destroy).  See include/dynamite_amd.h for the reference
 // interfaces each entry point replaces.
 #include "passes.h"
+#include "pm_rank.h"
 #include "vec_api.h"
 #include "row_fused.h"
 
@@ -536,6 +537,95 @@ int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t
   DNM_TRY(launch_zz_moments(x, s.dev, row0, nrows, scratch, m_dev, S(stream)));
   // (synchronises: the subspace tables are released on return)
   return dnm_memcpy_d2h(out, m_dev, D * D * sizeof(double), stream);
+}
+
+// ---- sigma+ sigma- moments ----------------------------------------------------------------------------------------
+// what the plan, the call and the partner table check alike, before any device call.  The pass brings its own
+// binomials (sector k + 1), so that the descriptor's fields are read here and nothing else of it is used.
+static int pm_check(const dnm_subspace *sub, const char *what) {
+  DNM_CHECK(sub, "%s: null subspace descriptor", what);
+  DNM_CHECK(sub->type != DNM_EXPLICIT, "%s: Explicit subspaces are not supported (the partners of a row have no "
+            "closed-form index there)", what);
+  DNM_CHECK(sub->type == DNM_FULL || sub->type == DNM_PARITY || sub->type == DNM_SPIN_CONSERVE,
+            "%s: unknown subspace type %d", what, sub->type);
+  DNM_CHECK(sub->L >= 1 && sub->L <= 64, "%s: L=%lld out of range (at most 64 spins)", what, (long long)sub->L);
+  if (sub->type == DNM_SPIN_CONSERVE) {
+    DNM_CHECK(sub->k >= 0 && sub->k <= sub->L, "%s: bad SpinConserve descriptor (k=%lld)", what, (long long)sub->k);
+    DNM_CHECK(sub->vec_swizzle == 0, "%s: a SpinConserve state is read in reference order (vec_swizzle %d given: "
+              "dnm_vec_layout_copy converts)", what, sub->vec_swizzle);
+    DNM_CHECK(sub->site_perm == nullptr, "%s: no relabelled subspace (site_perm given): hand over the state in "
+              "reference order with a descriptor without it", what);
+  } else {
+    DNM_CHECK(sub->site_perm == nullptr, "%s: site_perm given for a subspace that is not SpinConserve", what);
+    DNM_CHECK(sub->vec_swizzle == 0 || (sub->vec_swizzle >= 5 && sub->vec_swizzle <= 24),
+              "%s: vec_swizzle %d: the shift of a swizzled vector lies in [5, 24]", what, sub->vec_swizzle);
+    if (sub->type == DNM_PARITY) DNM_CHECK(sub->space == 0 || sub->space == 1, "%s: parity space must be 0 or 1", what);
+  }
+  return 0;
+}
+
+int dnm_pm_moments_plan(const dnm_subspace *sub, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                        size_t *lds_bytes, size_t *scratch_bytes) {
+  DNM_TRY(pm_check(sub, "sigma+ sigma- moments"));
+  PmPlan p;
+  DNM_TRY(pm_plan(sub->type, (int)sub->L, (int)sub->k, &p));
+  if (tile_rows) *tile_rows = p.nb;
+  if (panel_rows_log2) *panel_rows_log2 = p.B;
+  if (nworkgroups) *nworkgroups = p.nwg;
+  if (lds_bytes) *lds_bytes = p.lds_bytes;
+  if (scratch_bytes) *scratch_bytes = p.partial_bytes;
+  return 0;
+}
+
+int dnm_pm_moments(const void *x, const dnm_subspace *sub, double *out, void *stream) {
+  DNM_CHECK(x && out, "sigma+ sigma- moments: null argument");
+  DNM_TRY(pm_check(sub, "sigma+ sigma- moments"));
+  const int L = (int)sub->L;
+  PmPlan p;
+  DNM_TRY(pm_plan(sub->type, L, (int)sub->k, &p));
+  const size_t obytes = (size_t)L * (size_t)L * 2 * sizeof(double);
+  if (p.nrows == 0) {       // SpinConserve(L, L): no configuration has a spin left to lower
+    memset(out, 0, obytes);
+    return 0;
+  }
+  std::vector<int64_t> nck;
+  if (sub->type == DNM_SPIN_CONSERVE) {
+    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
+    pm_binomials(L, p.K, L + 1, nck.data());
+  }
+  DevBuf big;
+  void *scratch = nullptr;       // the partial tiles, the matrix, the binomials
+  DNM_TRY(rdm_scratch(p.partial_bytes + obytes + p.table_bytes, &big, &scratch, "sigma+ sigma- moments",
+                      (long long)(p.partial_bytes / 2048 / (size_t)p.nwg), 16, p.nwg));
+  void *p_dev = (char *)scratch + p.partial_bytes;
+  int64_t *t_dev = (int64_t *)((char *)p_dev + obytes);
+  if (!nck.empty())
+    DNM_HIP(hipMemcpyAsync(t_dev, nck.data(), nck.size() * sizeof(int64_t), hipMemcpyHostToDevice, S(stream)));
+  DNM_TRY(launch_pm_moments(x, sub->type, L, (int)sub->k, (int)sub->space, sub->vec_swizzle, p, t_dev, scratch, p_dev,
+                            S(stream)));
+  // (synchronises: `big` and the host table are released on return)
+  return dnm_memcpy_d2h(out, p_dev, obytes, stream);
+}
+
+int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *rows, int64_t *out) {
+  DNM_TRY(pm_check(sub, "sigma+ sigma- partner indices"));
+  DNM_CHECK(sub->type == DNM_SPIN_CONSERVE, "sigma+ sigma- partner indices: SpinConserve only (Full and Parity "
+            "partners are index ^ mask)");
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && out)), "sigma+ sigma- partner indices: null argument");
+  const int L = (int)sub->L;
+  PmPlan p;
+  DNM_TRY(pm_plan(sub->type, L, (int)sub->k, &p));
+  std::vector<int64_t> nck((size_t)(p.K + 1) * (size_t)(L + 1));
+  if (p.nrows) pm_binomials(L, p.K, L + 1, nck.data());
+  for (int64_t i = 0; i < n; ++i) {
+    DNM_CHECK(rows[i] >= 0 && rows[i] < p.nrows, "sigma+ sigma- partner indices: row %lld of a sector of %lld rows "
+              "(%d set bits)", (long long)rows[i], (long long)p.nrows, p.K);
+    int64_t *o = out + i * L;
+    for (int j = 0; j < L; ++j) o[j] = -1;
+    pm_partners(pm_unrank(rows[i], L, p.K, nck.data(), L + 1), nck.data(), L + 1,
+                [&](int j, int64_t idx) { o[j] = idx; });
+  }
+  return 0;
 }
 
 // ---- shell matrix -------------------------------------------------------------

@@ -264,6 +264,16 @@ class State:
         from . import computations
         return computations.sigmaz_correlations(self, connected=connected)
 
+    def sigma_pm_correlations(self):
+        """``pm[i, j]`` = <sigma_plus(i) sigma_minus(j)> for every pair in one pass -> computations.sigma_pm_correlations."""
+        from . import computations
+        return computations.sigma_pm_correlations(self)
+
+    def spin_correlations(self):
+        """``ss[i, j]`` = <sigma_i . sigma_j> for every pair -> computations.spin_correlations."""
+        from . import computations
+        return computations.spin_correlations(self)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

@@ -214,6 +214,33 @@ int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size,
 int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
                         size_t *scratch_bytes);
 int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream);
+/* Every <sigma+_i sigma-_j> of a state in one pass over it -- the transverse part <sigmax_i sigmax_j + sigmay_i sigmay_j>
+ * of the spin correlations, where the call above gives the sigmaz part (no counterpart in the reference, whose users
+ * call Operator.expectation once per pair).  sigma_minus(j) = sigmax_j - i sigmay_j sets bit j of a configuration with
+ * matrix element 2, sigma_plus is its adjoint.  With A[r][j] = x(r ^ e_j) on the configurations r whose bit j is set
+ * and 0 elsewhere,
+ *   P[i][j] = sum_r conj(A[r][i]) A[r][j]      (L x L complex128, row-major, Hermitian),
+ * so that <x|sigma_plus(i) sigma_minus(j)|x> = 4 P[i][j] -- an exact scaling -- and P[i][i] = the weight of the
+ * configurations whose bit i is clear, (M[0][0] + M[0][1+i]) / 2 of dnm_zz_moments.  Sums are raw (nothing is
+ * normalised).  P equals its conjugate transpose to the last bit, its diagonal is real, and two calls return the same
+ * bits on any device (no atomics; the number of workgroups follows from the subspace alone).
+ * x (device) is the WHOLE state on one device.  Layouts: Full / Parity in index order (vec_swizzle 0) or XOR-swizzled,
+ * read as it lies; SpinConserve(L, k) in reference order -- the rows r are then the configurations with k + 1 set bits,
+ * and k = L gives P = 0 without a launch.  Refused, each before any device call: Explicit subspaces, the SpinConserve
+ * internal layout and a non-null site_perm (the caller converts: dnm_vec_layout_copy), L > 64, null pointers.
+ * out: HOST, L * L * 2 doubles (re, im); the call synchronises the stream like dnm_vec_dot.  Scratch comes from the
+ * library's workspace (dnm_release_workspace).
+ * dnm_pm_moments_plan (host only, no device needed): tile_rows = ceil(L / 16) rows of 16 x 16 tiles (NB), the panel
+ * of 2^panel_rows_log2 rows of A a workgroup stages in LDS, the workgroups of the sweep, the bytes of LDS of a launch
+ * (at least the panel, 2^panel_rows_log2 * 16 NB * 16, at most 160 KB) and the bytes of the partial tiles,
+ * nworkgroups * (NB (NB + 1) / 2 + NB^2) * 256 * 8; any output may be null.
+ * dnm_pm_partner_indices (host only, SpinConserve only): for each of the n rows -- indices in the sector with k + 1 set
+ * bits -- out[row * L + j] = the index in sector k of the row's configuration with bit j cleared, or -1 where bit j
+ * is clear.  The arithmetic is the kernel's (csrc/pm_rank.h). */
+int dnm_pm_moments_plan(const dnm_subspace *sub, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                        size_t *lds_bytes, size_t *scratch_bytes);
+int dnm_pm_moments(const void *x, const dnm_subspace *sub, double *out, void *stream);
+int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *rows, int64_t *out);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
