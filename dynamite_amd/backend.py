@@ -1866,6 +1866,69 @@ def pm_moments(vec, subspace):
     return out
 
 
+def _bonds_c(bonds):
+    bonds = np.ascontiguousarray(bonds, dtype=np.int32).reshape(-1, 2)
+    return bonds, bonds.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def swap_moments_plan(sub_c, nbonds):
+    """``dnm_swap_moments_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
+    launch, bytes of the partial tiles) of the bond-swap sweep with ``nbonds`` bonds over a state of the subspace."""
+    tr, pb, nw, lb, sb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_swap_moments_plan(C.byref(sub_c), int(nbonds), C.byref(tr), C.byref(pb), C.byref(nw),
+                                                C.byref(lb), C.byref(sb)))
+    return tr.value, pb.value, nw.value, int(lb.value), int(sb.value)
+
+
+def swap_partner_indices(sub_c, bonds, rows, xparity_sector=0):
+    """``dnm_swap_partner_indices`` (host only): ``(idx, sign)``, int64 and int8 arrays (len(rows), len(bonds)) -- for
+    the row of index ``rows[n]`` of the vector and bond m, the reference-order index into the vector of that row's
+    configuration with the two spins of the bond exchanged, and its factor: +1, or ``xparity_sector`` where the
+    exchange sets bit L - 1 and the amplitude is the complement's."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    bonds, bp = _bonds_c(bonds)
+    idx = np.empty((rows.size, bonds.shape[0]), dtype=np.int64)
+    sign = np.empty((rows.size, bonds.shape[0]), dtype=np.int8)
+    _lib.check(_lib.lib().dnm_swap_partner_indices(C.byref(sub_c), int(xparity_sector), bonds.shape[0], bp, rows.size,
+                                                   _lib.p64(rows), _lib.p64(idx),
+                                                   sign.ctypes.data_as(C.POINTER(C.c_int8))))
+    return idx, sign
+
+
+def swap_moments(vec, subspace, bonds, xparity_sector=0):
+    """The raw bond-swap moments of the state in ``vec`` in one pass: numpy array G of shape (n + 1, n + 1), complex128,
+    for the n <= 63 bonds ``bonds`` = [(a_0, b_0), ...]: G = A^H A with A[r, 0] = psi(r) and A[r, 1 + m] = psi(r with
+    bits a_m and b_m exchanged), so that G[0, 0] = <psi|psi>, G[0, 1 + m] = <P_m> and G[1 + m, 1 + m'] = <P_m P_m'> for
+    the exchange P_m of the two spins (raw sums, nothing normalised; G is Hermitian to the last bit).  ``subspace`` is
+    the descriptor of the Full, Parity or SpinConserve subspace of the vector -- with ``xparity_sector`` = +-1 that of
+    the parent of the XParity subspace whose representatives the vector holds.  Swizzled Full / Parity vectors are read
+    as they lie; a SpinConserve vector in the internal layout is converted to reference order first (one extra
+    vector).  The partners of a rank's rows lie on other ranks: on more than one rank this raises
+    ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('bond-swap moments of a partitioned state: the partner amplitudes of a rank\'s rows '
+                                  'lie on other ranks')
+    sub_c = subspace['data']
+    x = vec.array
+    if vec.internal:
+        x = vec.local_natural()
+        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
+        sub_c.vec_swizzle = 0
+        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    bonds, bp = _bonds_c(bonds)
+    n = bonds.shape[0]
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
+    expect = full.value // 2 if xparity_sector else full.value
+    if x.numel() != expect:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), expect))
+    out = np.empty((n + 1, n + 1), dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_swap_moments(C.c_void_p(x.data_ptr()), C.byref(sub_c), int(xparity_sector), n, bp,
+                                           out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return out
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -705,6 +705,78 @@ def spin_correlations(state):
     return ss
 
 
+_SWAP_CALL_MAX = 63       # bonds of one call of backend.swap_moments
+_SWAP_CHUNK = 31          # longer lists: chunks of this size, one call per pair of chunks on their union
+
+
+def _swap_subspace(state):
+    """(descriptor's subspace, XParity sector or 0) for the bond-swap pass: Full, Parity and SpinConserve, and XParity
+    over those (the descriptor is then the parent's)."""
+    from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
+    sp = state.subspace
+    base, sector = (sp.parent, int(sp.sector)) if type(sp) is XParity else (sp, 0)
+    if isinstance(base, Explicit) or not isinstance(base, (Full, Parity, SpinConserve)):
+        raise ValueError('bond correlations need a Full, Parity or SpinConserve subspace, or XParity over one of them, '
+                         'not %r' % (sp,))
+    return sp, sector
+
+
+def _swap_gram(state, bonds):
+    """G of backend.swap_moments for any number of bonds: G[0, 0], G[0, 1 + m] and G[1 + m, 1 + m']."""
+    from . import backend
+    sp, sector = _swap_subspace(state)
+    sub_c = sp._to_c()
+    n = len(bonds)
+    if n <= _SWAP_CALL_MAX:
+        return backend.swap_moments(state.vec, sub_c, bonds, sector)
+    G = np.zeros((n + 1, n + 1), dtype=np.complex128)
+    chunks = [np.arange(lo, min(lo + _SWAP_CHUNK, n)) for lo in range(0, n, _SWAP_CHUNK)]
+    for i in range(len(chunks)):
+        for j in range(i + 1, len(chunks)):
+            # (with more than one chunk every chunk has a partner: the diagonal blocks come with the pairs)
+            sel = np.concatenate([chunks[i], chunks[j]])
+            g = backend.swap_moments(state.vec, sub_c, bonds[sel], sector)
+            at = np.concatenate([[0], 1 + sel])
+            G[np.ix_(at, at)] = g
+    return G
+
+
+def bond_correlations(state, bonds, connected=False):
+    """Every bond energy and every bond-bond (dimer-dimer) correlator of ``state`` from one pass over it (one
+    matrix-core kernel, ``backend.swap_moments``) instead of one ``Operator.expectation`` per pair of bonds.  ``bonds``
+    is a list of pairs of sites (a_m, b_m), a_m != b_m; a bond may repeat and bonds may share sites.  Returns
+    ``(b, bb)``: ``b[m]`` = <psi|sigma_a . sigma_b|psi>, float64, and ``bb[m, m']`` = <psi|(sigma_a . sigma_b)(sigma_c .
+    sigma_d)|psi>, complex128 and Hermitian (real for a real state), with sigma . sigma = sigmax sigmax + sigmay sigmay
+    + sigmaz sigmaz and nothing normalised, as ``expectation`` normalises nothing.  ``connected``: ``bb`` is ``bb / n -
+    outer(b, b) / n**2`` with n = <psi|psi>, the connected correlator of the normalised state.
+
+    sigma_a . sigma_b = 2 P_ab - 1 with P_ab the exchange of the two spins, so both come from the Gram matrix G of the
+    swapped amplitudes: ``b[m] = 2 G[0, 1 + m] - G[0, 0]`` and ``bb[m, m'] = 4 G[1 + m, 1 + m'] - 2 G[1 + m, 0] - 2 G[0, 1
+    + m'] + G[0, 0]``.  An exchange commutes with the global spin flip: states on XParity subspaces are served as they
+    lie.  Full, Parity and SpinConserve states and XParity over those, on one process.  One call of the kernel takes 63
+    bonds; longer lists are cut into chunks of 31 and every pair of chunks takes one call."""
+    state.assert_initialized()
+    config._initialize()
+    sp, _ = _swap_subspace(state)
+    bonds = np.asarray(bonds, dtype=np.int64)
+    if bonds.size == 0:
+        raise ValueError('bond correlations of an empty list of bonds')
+    if bonds.ndim != 2 or bonds.shape[1] != 2:
+        raise ValueError('bonds must be pairs of sites, not an array of shape %r' % (bonds.shape,))
+    if bonds.min() < 0 or bonds.max() >= sp.L:
+        raise ValueError('a bond has a site outside [0, %d)' % sp.L)
+    if np.any(bonds[:, 0] == bonds[:, 1]):
+        raise ValueError('a bond joins a site to itself')
+    G = _swap_gram(state, bonds)
+    n = G[0, 0].real
+    b = 2.0 * G[0, 1:].real - n
+    # (the two cross terms are added to each other first: bb is then Hermitian to the last bit, as G is)
+    bb = 4.0 * G[1:, 1:] - 2.0 * (G[1:, :1] + G[:1, 1:]) + G[0, 0]
+    if connected:
+        bb = bb / n - np.outer(b, b) / n ** 2
+    return b, bb
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

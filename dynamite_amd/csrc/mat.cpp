@@ -3,6 +3,7 @@
 // interfaces each entry point replaces.
 #include "passes.h"
 #include "pm_rank.h"
+#include "swap_rank.h"
 #include "vec_api.h"
 #include "row_fused.h"
 
@@ -624,6 +625,108 @@ int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *ro
     for (int j = 0; j < L; ++j) o[j] = -1;
     pm_partners(pm_unrank(rows[i], L, p.K, nck.data(), L + 1), nck.data(), L + 1,
                 [&](int j, int64_t idx) { o[j] = idx; });
+  }
+  return 0;
+}
+
+// ---- bond-swap moments --------------------------------------------------------------------------------------------
+// what the plan, the call and the partner table check alike, before any device call (bonds: null for the plan)
+static int swap_check(const dnm_subspace *sub, int xsec, int nbonds, const int32_t *bonds) {
+  const char *what = "bond-swap moments";
+  DNM_TRY(pm_check(sub, what));
+  DNM_CHECK(xsec == 0 || xsec == 1 || xsec == -1, "%s: xparity_sector %d (0, +1 or -1)", what, xsec);
+  if (xsec != 0) {
+    DNM_CHECK(sub->L >= 2, "%s: an XParity sector of L=%lld", what, (long long)sub->L);
+    if (sub->type == DNM_PARITY)
+      DNM_CHECK(sub->L % 2 == 0, "%s: Parity carries the global flip of XParity only when L is even (L=%lld)", what,
+                (long long)sub->L);
+    if (sub->type == DNM_SPIN_CONSERVE)
+      DNM_CHECK(sub->L == 2 * sub->k, "%s: SpinConserve carries the global flip of XParity only when k = L / 2 "
+                "(L=%lld, k=%lld)", what, (long long)sub->L, (long long)sub->k);
+  }
+  DNM_CHECK(nbonds >= 1 && nbonds <= 63, "%s: %d bonds (1 to 63 in one call)", what, nbonds);
+  for (int m = 0; bonds && m < nbonds; ++m) {
+    const int a = bonds[2 * m], b = bonds[2 * m + 1];
+    DNM_CHECK(a >= 0 && a < sub->L && b >= 0 && b < sub->L, "%s: bond %d = (%d, %d) has a site outside [0, %lld)", what,
+              m, a, b, (long long)sub->L);
+    DNM_CHECK(a != b, "%s: bond %d joins site %d to itself", what, m, a);
+  }
+  return 0;
+}
+
+int dnm_swap_moments_plan(const dnm_subspace *sub, int nbonds, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                          size_t *lds_bytes, size_t *scratch_bytes) {
+  DNM_TRY(swap_check(sub, 0, nbonds, nullptr));
+  SwapPlan p;
+  DNM_TRY(swap_plan(sub->type, (int)sub->L, (int)sub->k, nbonds, 0, &p));
+  if (tile_rows) *tile_rows = p.nb;
+  if (panel_rows_log2) *panel_rows_log2 = p.B;
+  if (nworkgroups) *nworkgroups = p.nwg;
+  if (lds_bytes) *lds_bytes = p.lds_bytes;
+  if (scratch_bytes) *scratch_bytes = p.partial_bytes;
+  return 0;
+}
+
+int dnm_swap_moments(const void *x, const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds,
+                     double *out, void *stream) {
+  DNM_CHECK(x && out && bonds, "bond-swap moments: null argument");
+  DNM_TRY(swap_check(sub, xparity_sector, nbonds, bonds));
+  const int L = (int)sub->L;
+  SwapPlan p;
+  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, nbonds, xparity_sector, &p));
+  const size_t D = (size_t)nbonds + 1, obytes = D * D * 2 * sizeof(double);
+  std::vector<int64_t> nck;
+  if (sub->type == DNM_SPIN_CONSERVE) {
+    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
+    pm_binomials(L, p.K, L + 1, nck.data());
+  }
+  DevBuf big;
+  void *scratch = nullptr;       // the partial tiles, the matrix, the binomials
+  DNM_TRY(rdm_scratch(p.partial_bytes + obytes + p.table_bytes, &big, &scratch, "bond-swap moments",
+                      (long long)(p.partial_bytes / 2048 / (size_t)p.nwg), 16, p.nwg));
+  void *g_dev = (char *)scratch + p.partial_bytes;
+  int64_t *t_dev = (int64_t *)((char *)g_dev + obytes);
+  if (!nck.empty())
+    DNM_HIP(hipMemcpyAsync(t_dev, nck.data(), nck.size() * sizeof(int64_t), hipMemcpyHostToDevice, S(stream)));
+  DNM_TRY(launch_swap_moments(x, sub->type, L, (int)sub->space, sub->vec_swizzle, xparity_sector, nbonds, bonds, p,
+                              t_dev, scratch, g_dev, S(stream)));
+  // (synchronises: `big` and the host table are released on return)
+  return dnm_memcpy_d2h(out, g_dev, obytes, stream);
+}
+
+int dnm_swap_partner_indices(const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds, int64_t n,
+                             const int64_t *rows, int64_t *idx, int8_t *sign) {
+  DNM_CHECK(bonds, "bond-swap partner indices: null argument");
+  DNM_TRY(swap_check(sub, xparity_sector, nbonds, bonds));
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "bond-swap partner indices: null argument");
+  const int L = (int)sub->L;
+  SwapPlan p;
+  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, nbonds, xparity_sector, &p));
+  const bool sc = sub->type == DNM_SPIN_CONSERVE, parity = sub->type == DNM_PARITY;
+  std::vector<int64_t> nck;
+  if (sc) {
+    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
+    pm_binomials(L, p.K, L + 1, nck.data());
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t row = rows[i];
+    DNM_CHECK(row >= 0 && row < p.nrows, "bond-swap partner indices: row %lld of %lld rows", (long long)row,
+              (long long)p.nrows);
+    const uint64_t cfg = sc ? pm_unrank(row, L, p.K, nck.data(), L + 1)
+                         : parity ? ((uint64_t)row << 1) | (uint64_t)(hd_par((uint64_t)row) ^ (int)sub->space)
+                                  : (uint64_t)row;
+    for (int m = 0; m < nbonds; ++m) {
+      const int a = bonds[2 * m], b = bonds[2 * m + 1];
+      int fl = 0;
+      int64_t at = row;
+      if (sc) {
+        at = swap_sc_partner(cfg, row, a, b, L, p.dim, xparity_sector, nck.data(), L + 1, &fl);
+      } else if (((cfg >> a) ^ (cfg >> b)) & 1) {
+        at = row ^ (int64_t)swap_index_mask(parity, L, a, b, xparity_sector, &fl);
+      }
+      idx[i * nbonds + m] = at;
+      sign[i * nbonds + m] = (int8_t)(fl ? xparity_sector : 1);
+    }
   }
   return 0;
 }

@@ -274,6 +274,12 @@ class State:
         from . import computations
         return computations.spin_correlations(self)
 
+    def bond_correlations(self, bonds, connected=False):
+        """``(b, bb)``: every <sigma_a . sigma_b> and <(sigma_a . sigma_b)(sigma_c . sigma_d)> of the bonds in one pass
+        -> computations.bond_correlations."""
+        from . import computations
+        return computations.bond_correlations(self, bonds, connected=connected)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

@@ -241,6 +241,39 @@ int dnm_pm_moments_plan(const dnm_subspace *sub, int *tile_rows, int *panel_rows
                         size_t *lds_bytes, size_t *scratch_bytes);
 int dnm_pm_moments(const void *x, const dnm_subspace *sub, double *out, void *stream);
 int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *rows, int64_t *out);
+/* Every bond-swap (dimer-dimer) correlator of a state in one pass over it (no counterpart in the reference, whose users
+ * call Operator.expectation once per pair of bonds).  sigma_a . sigma_b = 2 P_ab - 1 with P_ab the exchange of the spins
+ * a and b.  For nbonds bonds (a_m, b_m) = (bonds[2 m], bonds[2 m + 1]), a_m != b_m -- a bond may repeat, bonds may
+ * share sites -- and the operand matrix over the rows r of the subspace
+ *   A[r][0] = x(r),   A[r][1 + m] = x(r with bits a_m and b_m exchanged),
+ *   G = A^H A      ((nbonds + 1) x (nbonds + 1) complex128, row-major, Hermitian):
+ * G[0][0] = <x|x>, G[0][1 + m] = <P_m>, G[1 + m][1 + m'] = <P_m P_m'>.  Sums are raw (nothing is normalised).  G equals
+ * its conjugate transpose to the last bit, its diagonal is real, and two calls return the same bits on any device (no
+ * atomics; the number of workgroups follows from the number of rows alone).
+ * x (device) is the WHOLE state on one device.  Layouts: Full / Parity in index order or XOR-swizzled, read as it lies;
+ * SpinConserve in reference order.  xparity_sector = +-1: x holds the dim / 2 amplitudes of the representatives of that
+ * XParity sector and sub is the parent's descriptor (the convention of dnm_rdm_sector_blocks); a swap commutes with the
+ * global flip, so the sum over the representatives -- with the partner of a row taken as the sector's sign times the
+ * amplitude of its complement where the swap sets bit L - 1 -- is the expectation value in the sector.
+ * Refused, each before any device call: null pointers, Explicit subspaces, an unknown subspace type, L outside [1, 64],
+ * nbonds outside [1, 63], a site outside [0, L) or a_m == b_m, a non-null site_perm, the SpinConserve internal layout
+ * (the caller converts: dnm_vec_layout_copy), a Full / Parity swizzle shift outside {0} and [5, 24], xparity_sector
+ * other than 0, +1, -1, and an XParity parent that cannot carry the flip (Parity with odd L, SpinConserve with L != 2 k).
+ * out: HOST, (nbonds + 1)^2 * 2 doubles (re, im); the call synchronises the stream like dnm_vec_dot.  Scratch comes
+ * from the library's workspace (dnm_release_workspace).
+ * dnm_swap_moments_plan (host only, no device needed): tile_rows = ceil((nbonds + 1) / 16) rows of 16 x 16 tiles (NB),
+ * the panel of 2^panel_rows_log2 rows of A a workgroup stages in LDS, the workgroups of the sweep -- ceil(rows / 512),
+ * at most 1024 -- the bytes of LDS of a launch (at most 152 KB) and the bytes of the partial tiles, nworkgroups *
+ * (NB (NB + 1) / 2 + NB^2) * 256 * 8; any output may be null.
+ * dnm_swap_partner_indices (host only): for each of the n rows (indices into x) and each bond, idx[row * nbonds + m] =
+ * the reference-order index into x of the amplitude A[row][1 + m] is taken from and sign[row * nbonds + m] its factor:
+ * +1, or the sector where the complement's amplitude was taken.  The arithmetic is the kernel's (csrc/swap_rank.h). */
+int dnm_swap_moments_plan(const dnm_subspace *sub, int nbonds, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                          size_t *lds_bytes, size_t *scratch_bytes);
+int dnm_swap_moments(const void *x, const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds,
+                     double *out, void *stream);
+int dnm_swap_partner_indices(const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds, int64_t n,
+                             const int64_t *rows, int64_t *idx, int8_t *sign);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
