@@ -951,7 +951,13 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
     A->sc3.reset(new Sc3Mat());
     // partitioned: whole T blocks per rank (a contiguous range of both the internal layout and the reference order)
     std::vector<uint32_t> Tb = sc3_partition(*ly, A->nranks);
-    if (A->xparity) Tb = {0u, 1u << (ly->host.t - 1)};
+    if (A->xparity) {
+      // the half whose top bit is clear, as a PLACE in the block sequence (a layout with empty blocks -- k > a + w or
+      // t > k -- has fewer than 2^(t-1) blocks below it); only block order 0 keeps that half together
+      DNM_CHECK(ly->order == 0, "XParity on a SpinConserve layout in block order %d: the half whose top bit is clear is "
+                "no range of that layout", ly->order);
+      Tb = {0u, sc3_top_clear_blocks(*ly)};
+    }
     const bool want_real = (flags & DNM_MAT_REAL_PACKED) != 0;
     // site relabelling of the vectors (dnm_subspace.site_perm): the kernels of the layout see the operator in it
     Sc3Perm P, Pr;
@@ -1009,7 +1015,11 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
     sc3_range(*ly, Tb[A->rank], Tb[A->rank + 1], &is, &il, &ns, &nl);
     A->m_local = A->n_local = il;          // what the vector kernels sweep: rows + padding
     A->rows_local = nl;
-    A->row0 = ns;                          // first row in reference order (norm / diagonal kernels)
+    // first row in reference order (norm / diagonal kernels).  Block order 0: the share is the reference rows
+    // [row0, row0 + rows_local).  Any other order: rows_local still counts the share's rows, but they are no range of
+    // the reference order and row0 is -1 on every share that does not start the sequence -- whatever walks reference
+    // rows asks ref_side first or walks sc3_ref_runs (dnm_mat_norm_inf)
+    A->row0 = ns;
     if (want_real) {
       // real vectors in the same positions of the layout, one double each: a vector is il / 2 complex128 elements for
       // everything that sweeps it (the Krylov kernels); the two tiled passes only (chain operators, real symmetric)
@@ -1273,7 +1283,10 @@ int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream) {
             "precomputed diagonal is not used by the partitioned tiled multiply");
   DNM_CHECK(A->M == A->N, "precompute_diagonal needs a square matrix");
   if (A->use_sc3) {
-    // computed row by row in reference order, kept in the vectors' layout
+    // computed row by row in reference order, kept in the vectors' layout: the share needs a reference side (every share
+    // of block order 0, whole vectors of the others) -- asked before anything is launched
+    DNM_TRY(ref_side(*A->sc3->ly, row_range(*A->sc3->ly, A->sc3->T0, A->sc3->T1)));
+    DNM_CHECK(A->row0 >= 0, "internal: a share with a reference side has no first reference row");
     DevBuf nat;
     DNM_TRY(nat.alloc((size_t)A->rows_local * sizeof(double)));
     DNM_TRY(launch_diag(A->dmsc, A->right.dev, A->rows_local, A->row0, (double *)nat.p, S(stream)));
@@ -1644,6 +1657,7 @@ int dnm_mat_window_local_rows(dnm_mat *A, int64_t col_lo, int64_t col_hi, int ma
   *nranges = 0;
   if (A->use_sc3 || A->host_only || (A->hypercube && A->plan.use_tiled) || A->m_local <= 0) return 0;
   if (A->left.host.swz != 0) return 0;       // a swizzled result block is not a sequence of row ranges
+  DNM_CHECK(A->row0 >= 0, "internal: no first row in reference order");      // (the sweep below walks reference rows)
   const int64_t per = A->sc_pair ? sc_rows_per_block() : gather_rows_per_block();
   const int nb = A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local);
   DevBuf buf;
@@ -1768,12 +1782,32 @@ int dnm_mat_norm_inf(dnm_mat *A, double *nrm, void *stream) {
     *nrm = A->nrm;
     return 0;
   }
-  const int nb = norm_num_blocks(A->rows_local);
-  DNM_TRY(A->scratch.alloc((size_t)nb * sizeof(double)));
-  DNM_TRY(launch_norm(A->dmsc, A->left.dev, A->right.dev, A->rows_local, A->row0,
-                      (double *)A->scratch.p, S(stream)));
+  // The rows this handle sweeps, as runs of the reference order: [row0, row0 + rows_local) -- except a SpinConserve
+  // share in a block order other than 0 (the solver's partition), which is no range of that order: its blocks, merged
+  // where they follow each other in the reference order (one launch per run, once per handle: SpinConserve(36,18) on 8
+  // ranks has a few hundred blocks per rank)
+  std::vector<std::pair<int64_t, int64_t>> runs;
+  if (A->use_sc3 && A->sc3->ly->order != 0) runs = sc3_ref_runs(*A->sc3->ly, A->sc3->T0, A->sc3->T1);
+  else {
+    DNM_CHECK(A->row0 >= 0, "internal: no first row in reference order");
+    runs.push_back({A->row0, A->rows_local});
+  }
+  size_t nb = 0;
+  for (const auto &r : runs) {
+    DNM_CHECK(r.first >= 0 && r.second >= 0 && r.first + r.second <= A->left.host.dim,
+              "internal: rows [%lld, %lld + %lld) outside the subspace", (long long)r.first, (long long)r.first,
+              (long long)r.second);
+    nb += (size_t)norm_num_blocks(r.second);
+  }
+  DNM_TRY(A->scratch.alloc(std::max<size_t>(nb, 1) * sizeof(double)));
+  size_t at = 0;
+  for (const auto &r : runs) {
+    if (r.second == 0) continue;
+    DNM_TRY(launch_norm(A->dmsc, A->left.dev, A->right.dev, r.second, r.first, (double *)A->scratch.p + at, S(stream)));
+    at += (size_t)norm_num_blocks(r.second);
+  }
   std::vector<double> h(nb);
-  DNM_TRY(dnm_memcpy_d2h(h.data(), A->scratch.p, (size_t)nb * sizeof(double), stream));
+  if (nb) DNM_TRY(dnm_memcpy_d2h(h.data(), A->scratch.p, nb * sizeof(double), stream));
   double best = 0.0;
   for (double v : h) best = std::max(best, v);
   if (A->nranks == 1) A->nrm = best;   // partitioned: caller reduces, then dnm_mat_set_norm

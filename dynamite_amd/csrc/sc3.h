@@ -251,14 +251,27 @@ struct Sc3Call {
 // Partition of the layout over ranks: rank r owns the blocks [Tb[r], Tb[r+1]) of the block sequence (whole blocks, balanced
 // by internal length), i.e. a contiguous range of the internal layout -- and, in block order 0, of the reference order.
 // Tb has nranks + 1 entries.
+// What an operator handle keeps of its range (dnm_mat: row0, rows_local; Sc3Mat: T0, T1): block order 0 -- the range is the
+// reference rows [row0, row0 + rows_local); any other order -- rows_local counts the range's rows, but they are no range of
+// the reference order and row0 is sc3_range's nstart, -1 unless the range starts the sequence.  Whatever walks a handle's
+// rows in reference order walks sc3_ref_runs (the norm) or asks ref_side first and refuses (the cached diagonal, the
+// position maps, the layout copies).
 std::vector<uint32_t> sc3_partition(const Sc3Layout &ly, int nranks);
 // internal / reference offsets of the block range [T0, T1) of the sequence: start and length (block orders other than 0:
 // *nstart = -1 unless the range starts the sequence; *nlen = the states in the range)
 void sc3_range(const Sc3Layout &ly, uint32_t T0, uint32_t T1, int64_t *istart, int64_t *ilen, int64_t *nstart, int64_t *nlen);
+// the same range's reference side in ANY block order: its states as maximal runs (first index, count) of the reference
+// order, in the order the blocks lie in memory (block order 0: one run, [nstart, nstart + nlen)) -- what a sweep over the
+// rows of a rank's share walks (dnm_mat_norm_inf)
+std::vector<std::pair<int64_t, int64_t>> sc3_ref_runs(const Sc3Layout &ly, uint32_t T0, uint32_t T1);
+// the place in the block sequence where T's top bit turns on: the number of non-empty blocks with T < 2^(t-1).  Block
+// order 0 only (there the sequence ascends in T); with L = 2k the blocks [0, that place) are the first half of the layout
+// and of the reference order -- the vectors of XParity on top of the subspace.  0xffffffff in any other order.
+uint32_t sc3_top_clear_blocks(const Sc3Layout &ly);
 
 struct Sc3Mat {
   const Sc3Layout *ly = nullptr;
-  uint32_t T0 = 0, T1 = 0;         // the blocks of the layout's sequence this rank's rows cover
+  uint32_t T0 = 0, T1 = 0;         // the blocks of the layout's sequence this rank's rows cover (places, not values of T)
   int64_t row0 = 0;                // internal position of its first row
   std::vector<uint32_t> rowsel;    // its rows (T << w | W), for the row kernel
   std::vector<char> needT;         // T blocks its rows read (own blocks included)

@@ -396,6 +396,26 @@ void sc3_range(const Sc3Layout &ly, uint32_t T0, uint32_t T1, int64_t *istart, i
   *nlen = n;
 }
 
+std::vector<std::pair<int64_t, int64_t>> sc3_ref_runs(const Sc3Layout &ly, uint32_t T0, uint32_t T1) {
+  const uint32_t nb = (uint32_t)ly.tseq.size();
+  const uint32_t b0 = std::min(T0, nb), b1 = std::max(b0, std::min(T1, nb));
+  const int aw = ly.host.a + ly.host.w;
+  std::vector<std::pair<int64_t, int64_t>> out;
+  for (uint32_t b = b0; b < b1; ++b) {
+    const uint32_t T = ly.tseq[b];
+    const int64_t n0 = ly.nbase[T], cnt = hbinom(aw, ly.host.k - __builtin_popcount(T));
+    if (!out.empty() && out.back().first + out.back().second == n0) out.back().second += cnt;
+    else out.push_back({n0, cnt});
+  }
+  return out;
+}
+
+uint32_t sc3_top_clear_blocks(const Sc3Layout &ly) {
+  if (ly.order != 0) return 0xffffffffu;
+  const uint32_t top = 1u << (ly.host.t - 1);
+  return (uint32_t)(std::lower_bound(ly.tseq.begin(), ly.tseq.end(), top) - ly.tseq.begin());
+}
+
 void Sc3Mat::window(int64_t *lo, int64_t *hi) const {
   int64_t a = INT64_MAX, b = INT64_MIN;
   for (uint32_t T = 0; T < (uint32_t)needT.size(); ++T)

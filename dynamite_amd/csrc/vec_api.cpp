@@ -254,6 +254,7 @@ int dnm_vec_layout_positions_host(const dnm_subspace *s, const dnm_partition *pa
   if (!ly) return 1;
   uint32_t T0, T1;
   DNM_TRY(part_range(*ly, part, &T0, &T1));
+  DNM_TRY(ref_side(*ly, row_range(*ly, T0, T1)));      // (as sc3_positions: local reference indices need a reference side)
   int64_t is, il, ns, nl;
   sc3_range(*ly, T0, T1, &is, &il, &ns, &nl);
   SubView v{};

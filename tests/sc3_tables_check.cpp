@@ -409,7 +409,7 @@ static int run(const Case &c) {
   std::vector<uint32_t> Tb = sc3_partition(*ly, c.nranks);
   EXPECT(Tb.size() == (size_t)c.nranks + 1 && Tb.front() == 0 && Tb.back() == ly->tseq.size() &&
              std::is_sorted(Tb.begin(), Tb.end()), "%s: sc3_partition", c.name);
-  if (c.xparity) Tb = {0u, 1u << (ly->host.t - 1)};       // the blocks whose top bit is clear (dnm_mat_create)
+  if (c.xparity) Tb = {0u, sc3_top_clear_blocks(*ly)};    // the blocks whose top bit is clear (dnm_mat_create)
   const std::vector<ScMask> scm = sc_masks(c.op.masks, c.op.offs, c.op.signs, c.op.coef, c.L, c.xparity);
   int npair2 = 0;
   for (const ScMask &e : scm) npair2 += e.pair == 2;
@@ -441,7 +441,79 @@ static int run(const Case &c) {
   return 0;
 }
 
+// ---- block ranges as PLACES of the block sequence: layouts with empty blocks -----------------------------------
+// SpinConserve(L, L/2) in the (6, 4) layout from L = 22 on: k > a + w, so the blocks T = 0 and T = all ones are empty and
+// a place of the sequence is no value of T.  The half whose top bit is clear (XParity's vectors) ends at the place
+// sc3_top_clear_blocks names, and it is half of both index spaces; in block order 1 a share's reference side is the runs
+// of sc3_ref_runs: whole blocks, disjoint, all of the subspace over the ranks.
+static int check_places(int L, int a, int w) {
+  const int k = L / 2, failed_before = failures;
+  char name[32];
+  snprintf(name, sizeof name, "places(%d,%d)", L, k);
+  const Sc3Layout *ly = sc3_get(L, k, a, w, false, 0);
+  DNM_CHECK(ly, "no layout");
+  const uint32_t t = (uint32_t)ly->host.t, top = 1u << (t - 1), nb = (uint32_t)ly->tseq.size();
+  uint32_t full = 0, below = 0;            // the non-empty blocks (0 <= k - |T| <= a + w), counted
+  for (uint32_t T = 0; T < (1u << t); ++T)
+    if (k - pc(T) >= 0 && k - pc(T) <= a + w) { ++full; below += T < top; }
+  EXPECT(nb == full && full < (1u << t) && below < top && ly->ibase[0] < 0 && ly->ibase[(1u << t) - 1] < 0, "%s: %u blocks",
+         name, nb);
+  const uint32_t b = sc3_top_clear_blocks(*ly);
+  EXPECT(b == below && b == sc3_partition(*ly, 2)[1], "%s: the first half ends at place %u", name, b);
+  bool ok = std::is_sorted(ly->tseq.begin(), ly->tseq.end());
+  for (uint32_t j = 0; j < nb; ++j) ok = ok && (ly->tseq[j] < top) == (j < b) && ly->tidx[ly->tseq[j]] == j;
+  EXPECT(ok, "%s: the blocks below place %u are not those whose top bit is clear", name, b);
+  int64_t is, il, ns, nl;
+  sc3_range(*ly, 0, b, &is, &il, &ns, &nl);
+  EXPECT(is == 0 && ns == 0 && 2 * il == ly->host.nint && 2 * nl == ly->dim, "%s: first half [%lld + %lld), rows [%lld + %lld)",
+         name, (long long)is, (long long)il, (long long)ns, (long long)nl);
+  EXPECT(b < nb && ly->nbase[ly->tseq[b]] == ly->dim / 2 && 2 * ly->ibase[ly->tseq[b]] == ly->host.nint,
+         "%s: the block at place %u starts at row %lld", name, b, (long long)ly->nbase[ly->tseq[b]]);
+  const auto half = sc3_ref_runs(*ly, 0, b);
+  EXPECT(half.size() == 1 && half[0].first == 0 && half[0].second == ly->dim / 2, "%s: sc3_ref_runs of the first half", name);
+  // (what a value of T in place of the place would have taken: one block too many)
+  sc3_range(*ly, 0, top, &is, &il, &ns, &nl);
+  EXPECT(2 * nl > ly->dim && 2 * il > ly->host.nint, "%s: places [0, 2^(t-1)) hold %lld rows", name, (long long)nl);
+  // block order 1, three ranks
+  const Sc3Layout *l1 = sc3_get(L, k, a, w, false, 1);
+  DNM_CHECK(l1, "no layout in block order 1");
+  EXPECT(sc3_top_clear_blocks(*l1) == 0xffffffffu, "%s: a first half in block order 1", name);
+  const std::vector<uint32_t> Tb = sc3_partition(*l1, 3);
+  std::vector<std::pair<int64_t, int64_t>> all;
+  for (int r = 0; r < 3; ++r) {
+    const auto runs = sc3_ref_runs(*l1, Tb[r], Tb[r + 1]);
+    sc3_range(*l1, Tb[r], Tb[r + 1], &is, &il, &ns, &nl);
+    int64_t n = 0;
+    ok = !runs.empty() && ns == (r == 0 ? 0 : -1);
+    for (size_t i = 0; i < runs.size(); ++i) {
+      n += runs[i].second;
+      ok = ok && runs[i].first >= 0 && runs[i].second > 0 && runs[i].first + runs[i].second <= l1->dim;
+      ok = ok && (i == 0 || runs[i - 1].first + runs[i - 1].second != runs[i].first);       // maximal
+    }
+    EXPECT(ok && n == nl, "%s: rank %d of 3: %zu runs of %lld rows, the share has %lld", name, r, runs.size(), (long long)n,
+           (long long)nl);
+    EXPECT(runs.size() > 1, "%s: rank %d of 3 is a range of the reference order in block order 1", name, r);
+    all.insert(all.end(), runs.begin(), runs.end());
+  }
+  std::sort(all.begin(), all.end());
+  int64_t end = 0;
+  ok = true;
+  for (const auto &r : all) { ok = ok && r.first == end; end = r.first + r.second; }
+  EXPECT(ok && end == l1->dim, "%s: the shares' runs do not tile the reference order", name);
+  const auto whole = sc3_ref_runs(*l1, 0, 0xffffffffu);
+  int64_t n = 0;
+  for (const auto &r : whole) n += r.second;
+  EXPECT(n == l1->dim, "%s: the whole sequence has %lld rows", name, (long long)n);
+  if (failures == failed_before) printf("%-24s blocks as places: ok\n", name);
+  return 0;
+}
+
 int main() {
+  for (int L : {22, 24})
+    if (check_places(L, 6, 4)) {
+      ++failures;
+      printf("FAILED places(%d): %s\n", L, g_err);
+    }
   const std::vector<Case> cases = {
       {"chain12", chain12(), 12, 0, 1, false, false, false, true, false},
       {"graph13", graph13(false), 13, 0, 1, false, false, true, true, true},

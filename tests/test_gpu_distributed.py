@@ -419,6 +419,59 @@ def _worker(rank, world, port, case, out_dir):
                 for e_, v_ in zip(ev_[:2], vv_[:2]):
                     vg_ = v_.to_numpy(to_all=True)
                     assert np.linalg.norm(Hs @ vg_ - e_ * vg_) < 1e-7, "eigenvectors moved back from the solver's partition"
+        # The NORM of the solver's handle.  Its share is no range of the reference order, so a sweep of the reference rows
+        # [row0, row0 + rows_local) looks at about the first dim / world rows only -- and passes on an operator like the one
+        # above, whose large rows are everywhere.  Hp: the chain's hops plus planted fields, its largest row (alone) in the
+        # last quarter of the reference order; every coefficient dyadic, every row sum exact.
+        import row_sweep_ref as rsr
+        from dynamite_amd.operators import sigmax, sigmay, sigmaz, identity, op_sum
+        hops = lambda: op_sum(0.25 * (sigmax(i) * sigmax(i + 1) + sigmay(i) * sigmay(i + 1)) for i in range(L - 1))
+        Hp = hops() + 2.0 ** (L + 3) * rsr.planted_fields(L, int(sub.idx_to_state(dim - 38)))
+        Hp.L = L
+        Hp.add_subspace(sub)
+        sums = rsr.row_sums(rsr.marshal(Hp.copy(), L), sub, sub)
+        assert np.flatnonzero(sums == sums.max()).tolist() == [dim - 38] and dim - 38 >= 3 * dim // 4
+        want_norm = orc.infnorm(orc_msc(Hp), orc_sub(sub), orc_sub(sub))
+        assert want_norm == sums.max()
+        base_norm = Hp.infinity_norm(subspaces=(sub, sub))
+        assert abs(base_norm - want_norm) < 1e-12
+        for real in (False, True):
+            smp = Hp.get_solver_mat(sub, real)
+            assert (smp is not None) == (sm is not None)
+            if smp is not None:
+                assert smp.swz_right >> 16 == 1 and smp.real_packed == real
+                got_norm = smp.norm()
+                assert got_norm == base_norm and abs(got_norm - want_norm) < 1e-12, "norm of the solver's handle"
+        Hp.destroy_mat()
+        # ... and what takes that norm for its spectral bound: the Chebyshev expansion.  He: the hops plus
+        # (1 - Z_{L-1}) (1 - Z_{L-2}) sum_i Z_i Z_{i+1} -- the projector keeps the large diagonal on the states with both
+        # top spins down, the last quarter of the reference order.  (The sum runs over the bonds that are not inside the
+        # layout's low field, i >= a - 1 = 5: with those inside it the diagonal has more sign patterns than the passes
+        # evaluate on the fly, it would be cached, and get_solver_mat gives no handle for such an operator.)
+        He = hops() + (identity() - sigmaz(L - 1)) * (identity() - sigmaz(L - 2)) * \
+            op_sum(sigmaz(i) * sigmaz(i + 1) for i in range(5, L - 1))
+        He.L = L
+        He.add_subspace(sub)
+        sme = He.get_solver_mat(sub, False)
+        assert (sme is not None) == (sm is not None)
+        if sme is not None:
+            Hes = He.to_numpy(subspaces=(sub, sub), sparse=True)
+            if rank == 0:
+                # on the rows a sweep of [0, max nlen) sees, the row sums stay below half the spectral radius: with that
+                # for a bound the expansion diverges
+                Ad = Hes.toarray()
+                assert np.abs(Ad - Ad.conj().T).max() == 0 and np.abs(Ad.imag).max() == 0
+                radius = np.abs(np.linalg.eigvalsh(Ad.real)).max()
+                nmax = max(_b.layout_partition(d1, world, q)[3] for q in range(world))
+                assert np.abs(Ad[:nmax]).sum(axis=1).max() <= 0.5 * radius, (nmax, radius)
+            ze = He.evolve(x, t=0.6, algo='chebyshev')
+            assert _ev.last_mat is sme
+            assert sme.norm() == He.infinity_norm(subspaces=(sub, sub))
+            want_e = spla.expm_multiply(-0.6j * Hes, xg)
+            assert np.max(np.abs(ze.to_numpy(to_all=True) - want_e)) < 1e-8, "Chebyshev evolve on the solver's partition"
+        He.destroy_mat()
+        if rank == 0 and sm is not None:
+            open(os.path.join(out_dir, "solver_partition_%d" % world), "w").write("in use")
 
     # reduced density matrix / entropy of the partitioned state
     for keep in ([0, 1, 2], [L - 3, L - 2], [1, 5, L - 1]):
@@ -477,6 +530,20 @@ def _native_ran(H, case):
     kept.destroy()
 
 
+def _solver_partition_ran(out_dir, world):
+    """The "sc3" case checks the solver's own partition (Operator.get_solver_mat: block order 1) only where that partition
+    has something to share out; here, from the layout's host tables alone, that it has at this rank count -- no rank
+    without rows, none with more than 1.5 times its share (get_solver_mat's rule) -- and that the ranks found it so: the
+    checks on that partition are not vacuous."""
+    from dynamite_amd import _lib, backend
+    from dynamite_amd.subspaces import SpinConserve
+    d = _lib.Subspace.from_buffer_copy(SpinConserve(14, 7)._c())
+    d.vec_swizzle = 6 | (4 << 8) | (1 << 16)
+    rows = [backend.layout_partition(d, world, q)[3] for q in range(world)]
+    assert sum(rows) == 3432 and min(rows) > 0 and max(rows) <= 1.5 * sum(rows) / world, rows
+    assert os.path.exists(os.path.join(out_dir, "solver_partition_%d" % world)), "the solver's partition was not in use"
+
+
 FAKE_RCCL = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
 
 
@@ -500,6 +567,8 @@ def test_partitioned_end_to_end_one_gpu(tmp_path, case, world):
     import torch.multiprocessing as mp
     mp.spawn(_worker, args=(world, _free_port(), case, str(tmp_path)), nprocs=world, join=True)
     assert os.path.exists(os.path.join(str(tmp_path), "ok_%s_%d" % (case, world)))
+    if case == "sc3":
+        _solver_partition_ran(str(tmp_path), world)
 
 
 @pytest.mark.parametrize("case,world", [("full", 2), ("full", 4), ("full", 8), ("parity", 4), ("sc", 3), ("sc3", 2), ("sc3", 3),
@@ -524,6 +593,8 @@ def test_native_schedule_between_rank_processes(tmp_path, monkeypatch, case, wor
     before = {d for d in os.listdir("/dev/shm") if d.startswith("dnmfake_")}      # (what an earlier, failed run left)
     mp.spawn(_worker, args=(world, _free_port(), case, str(tmp_path)), nprocs=world, join=True)
     assert os.path.exists(os.path.join(str(tmp_path), "ok_%s_%d" % (case, world)))
+    if case == "sc3":
+        _solver_partition_ran(str(tmp_path), world)
     left = {d for d in os.listdir("/dev/shm") if d.startswith("dnmfake_")} - before
     assert not left, "mailboxes left behind: %r" % left
 

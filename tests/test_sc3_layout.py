@@ -268,3 +268,122 @@ def test_bond_graph_operator_plans_on_the_host():
     _lib.check(_lib.lib().dnm_mat_plan_describe(h, buf, len(buf)))
     assert "two-pass kernels, internal layout" in buf.value.decode() and "diagonal cached" in buf.value.decode()
     _lib.check(_lib.lib().dnm_mat_destroy(h))
+
+
+# ---- block ranges are PLACES of the block sequence; a share in block order 1 has no reference side --------------------
+
+def _order1(d):
+    d1 = _lib.Subspace.from_buffer_copy(d)
+    d1.vec_swizzle = int(d.vec_swizzle) | (1 << 16)
+    return d1
+
+
+@pytest.mark.parametrize("L,k", [(15, 7), (16, 8), (17, 8)])
+def test_positions_of_a_share_without_a_reference_side_are_refused(L, k):
+    """Block order 1 (the solver's partition, csrc/sc3.h: sc3_code_order): a rank's share is no range of the reference
+    order, so local reference indices mean nothing there -- dnm_vec_layout_positions_host refuses every share of P > 1
+    ranks (rank 0 too: its blocks are not the first rows either), as its device twin does; it used to answer with the
+    positions of the indices shifted by nstart = -1.  Whole vectors in order 1 and every share in order 0 keep working
+    and stay bijections onto the same positions."""
+    sub, d = _desc(L, k, 6, 4)
+    d1 = _order1(d)
+    n = sub.get_dimension()
+    nint = C.c_int64()
+    _lib.check(_lib.lib().dnm_vec_layout_size(C.byref(d1), C.byref(nint)))
+    p0, p1 = _positions(d, n), _positions(d1, n)
+    for p in (p0, p1, _positions(d1, n, _lib.Partition(0, 1))):
+        assert len(np.unique(p)) == n and p.min() >= 0 and p.max() < nint.value
+    assert not np.array_equal(p0, p1) and np.array_equal(p1, _positions(d1, n, _lib.Partition(0, 1)))
+    ragged = 0
+    for P in (2, 3):
+        seen = []
+        for r in range(P):
+            istart, ilen, nstart, nlen = backend.layout_partition(d1, P, r)
+            assert nstart == (0 if r == 0 else -1) and nlen > 0
+            with pytest.raises(_lib.BackendError, match="block order 1"):
+                _positions(d1, nlen, _lib.Partition(r, P))
+            # the share's rows are the reference indices whose whole-vector position lies in its range of the layout
+            rows = np.flatnonzero((p1 >= istart) & (p1 < istart + ilen))
+            assert rows.size == nlen
+            seen.append(rows)
+            # order 0: the local map is the whole map cut at the share
+            i0, il0, ns0, nl0 = backend.layout_partition(d, P, r)
+            assert np.array_equal(_positions(d, nl0, _lib.Partition(r, P)) + i0, p0[ns0:ns0 + nl0])
+        assert np.array_equal(np.sort(np.concatenate(seen)), np.arange(n))
+        ragged += sum(int(rows[-1] - rows[0] + 1 != rows.size) for rows in seen[1:])
+    assert ragged >= 2          # (not vacuous: shares beyond the first that are no range of the reference order)
+
+
+def _xparity_arrays(L):
+    """The Heisenberg chain reduced as XParity(SpinConserve(L, L/2), '+') reduces it."""
+    from dynamite_amd.subspaces import XParity
+    H = models.heisenberg(L)
+    H.establish_L()
+    H.reduce_msc()
+    red = XParity(SpinConserve(L, L // 2), '+').reduce_msc(H.msc)
+    masks, offs = msc_tools.get_mask_offsets(red)
+    return masks, offs, red['signs'], red['coeffs']
+
+
+@pytest.mark.parametrize("L", [14, 22, 24])
+def test_xparity_handle_takes_the_half_whose_top_bit_is_clear(L):
+    """XParity on top of SpinConserve(L, L/2) in the (6, 4) layout: the handle's vectors are the blocks whose top bit is
+    clear.  From L = 22 on the layout has empty blocks (k > a + w: T = 0 at L = 22, every T with fewer than two ones at
+    L = 24), the block sequence is shorter than 2^t and the half ends at a PLACE below 2^(t-1): the handle used to take
+    the place 2^(t-1) and with it blocks of the other half.  Its sizes are those of the first of two shares
+    (dnm_vec_layout_partition, what backend.Vec sizes an XParity vector by), half of both index spaces."""
+    sub, d = _desc(L, L // 2, 6, 4)
+    dim = sub.get_dimension()
+    nint = C.c_int64()
+    _lib.check(_lib.lib().dnm_vec_layout_size(C.byref(d), C.byref(nint)))
+    T, ib = backend.layout_blocks(d)
+    t = L - 10
+    assert (T.size < 1 << t) == (L >= 22) and np.all(np.diff(T) > 0)
+    place = int((T < 1 << (t - 1)).sum())
+    assert (place < 1 << (t - 1)) == (L >= 22)
+    istart, ilen, nstart, nlen = backend.layout_partition(d, 2, 0)
+    assert (istart, nstart) == (0, 0) and nlen == dim // 2 and ilen == nint.value // 2 == ib[place]
+    h = backend.create_mat(*_xparity_arrays(L), d, d, True, _lib.MAT_HOST_ONLY, 0, 1)
+    M, N, m, n = (C.c_int64() for _ in range(4))
+    _lib.check(_lib.lib().dnm_mat_sizes(h, C.byref(M), C.byref(N), C.byref(m), C.byref(n)))
+    row0, ml = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().dnm_mat_ownership(h, C.byref(row0), C.byref(ml)))
+    lo, hi = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().dnm_mat_column_window(h, C.byref(lo), C.byref(hi), None))
+    _lib.check(_lib.lib().dnm_mat_destroy(h))
+    assert (M.value, N.value) == (nlen, nlen) and (m.value, n.value) == (ilen, ilen)
+    assert (row0.value, ml.value) == (0, ilen)
+    assert (lo.value, hi.value) == (0, ilen - 1)          # the flip-composed hops stay inside the half
+    # ... and no XParity handle on a descriptor in block order 1, where that half is no range of the layout
+    with pytest.raises(_lib.BackendError, match="block order 1"):
+        backend.create_mat(*_xparity_arrays(L), _order1(d), _order1(d), True, _lib.MAT_HOST_ONLY, 0, 1)
+
+
+@pytest.mark.parametrize("a,w", [(6, 4), (14, 10)])
+def test_first_half_by_places_is_closed_under_the_complement(a, w):
+    """SpinConserve(L, L/2), every even L the layout takes (one to fifteen bits of T) up to 26: the first of two shares (whole blocks, cut by
+    places of the block sequence) ends exactly where T's top bit turns on -- half the positions, half the states, no
+    state of it has bit L-1 set, the next state has -- so the global flip maps the share onto the other one, which is
+    what XParity on top of the layout rests on."""
+    for L in range(a + w + 2 - (a + w) % 2, min(26, a + w + 15) + 1, 2):       # (1 <= t <= 15)
+        sub, d = _desc(L, L // 2, a, w)
+        dim = sub.get_dimension()
+        nint = C.c_int64()
+        _lib.check(_lib.lib().dnm_vec_layout_size(C.byref(d), C.byref(nint)))
+        T, ib = backend.layout_blocks(d)
+        t = L - a - w
+        place = int((T < 1 << (t - 1)).sum())
+        istart, ilen, nstart, nlen = backend.layout_partition(d, 2, 0)
+        assert (istart, nstart, 2 * ilen, 2 * nlen) == (0, 0, nint.value, dim), L
+        assert ib[place] == ilen and np.all(T[:place] < 1 << (t - 1)) and np.all(T[place:] >= 1 << (t - 1)), L
+        # the reference order ascends in the state: the last row of the share and the first one after it decide
+        last, nxt = (int(s) for s in sub.idx_to_state(np.array([nlen - 1, nlen])))
+        assert last >> (L - 1) == 0 and nxt >> (L - 1) == 1, L
+        edge = np.array([0, nlen - 1, nlen, dim - 1], dtype=np.int64)
+        pos = np.empty_like(edge)
+        _lib.check(_lib.lib().dnm_vec_layout_positions_host(C.byref(d), None, edge.size, _lib.p64(edge), _lib.p64(pos)))
+        assert pos[0] == 0 and pos[1] < ilen <= pos[2] and pos[3] < nint.value, L
+        if L <= 20:          # every state, where that is cheap
+            st = np.asarray(sub.idx_to_state(np.arange(dim)), dtype=np.int64)
+            p = _positions(d, dim)
+            assert np.array_equal(p < ilen, (st >> (L - 1)) == 0), L
