@@ -1696,13 +1696,23 @@ def _reduced_density_matrix(vec, subspace, keep):
             return rho if config.rank == 0 else None
         x, sub_c = _whole_state_on_rank0(vec, subspace)
         return None if x is None else rdm_partial(x, sub_c, keep)
-    sub_c = subspace['data']
-    if vec.internal:
-        # the kernel gathers by reference index: hand it the state in that order
-        x = vec.local_natural()
-        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
-        sub_c.vec_swizzle = 0
+    # (the kernel never reads site_perm: the descriptor keeps it)
+    x, sub_c = _reference_order(vec, subspace['data'], keep_perm=True)
     return rdm_partial(x, sub_c, keep)
+
+
+def _reference_order(vec, sub_c, keep_perm=False):
+    """``(device tensor, descriptor)`` for a kernel that gathers by reference index: a SpinConserve vector in the
+    internal layout is copied to reference order (one extra vector) under a copy of the descriptor that says so --
+    ``local_natural`` undoes the relabelling too, so ``site_perm`` goes unless ``keep_perm``; every other vector is
+    handed over as it lies."""
+    if not vec.internal:
+        return vec.array, sub_c
+    d = _lib.Subspace.from_buffer_copy(sub_c)
+    d.vec_swizzle = 0
+    if not keep_perm:
+        d.site_perm = None
+    return vec.local_natural(), d
 
 
 def rdm_sector_plan(sub_c, keep, xparity_sector=0):
@@ -1803,13 +1813,7 @@ def zz_moments(vec, subspace):
     density matrix: that costs one extra vector.  On several ranks each rank sweeps its block and the (L + 1)^2 sums
     are added over the ranks; every rank gets the result."""
     config._initialize()
-    sub_c = subspace['data']
-    x = vec.array
-    if vec.internal:
-        x = vec.local_natural()
-        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
-        sub_c.vec_swizzle = 0
-        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    x, sub_c = _reference_order(vec, subspace['data'])
     M = zz_moments_block(x, sub_c, vec.start, vec.rows)
     if _dist() is not None:
         from . import _comm
@@ -1848,13 +1852,7 @@ def pm_moments(vec, subspace):
     if _dist() is not None:
         raise NotImplementedError('sigma+ sigma- moments of a partitioned state: the partner amplitudes of a rank\'s '
                                   'rows lie on other ranks')
-    sub_c = subspace['data']
-    x = vec.array
-    if vec.internal:
-        x = vec.local_natural()
-        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
-        sub_c.vec_swizzle = 0
-        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    x, sub_c = _reference_order(vec, subspace['data'])
     L = int(sub_c.L)
     full = C.c_int64()
     _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
@@ -1909,13 +1907,7 @@ def swap_moments(vec, subspace, bonds, xparity_sector=0):
     if _dist() is not None:
         raise NotImplementedError('bond-swap moments of a partitioned state: the partner amplitudes of a rank\'s rows '
                                   'lie on other ranks')
-    sub_c = subspace['data']
-    x = vec.array
-    if vec.internal:
-        x = vec.local_natural()
-        sub_c = _lib.Subspace.from_buffer_copy(sub_c)
-        sub_c.vec_swizzle = 0
-        sub_c.site_perm = None          # (local_natural undoes the relabelling)
+    x, sub_c = _reference_order(vec, subspace['data'])
     bonds, bp = _bonds_c(bonds)
     n = bonds.shape[0]
     full = C.c_int64()

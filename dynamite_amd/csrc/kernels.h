@@ -161,38 +161,28 @@ void zz_plan(int L, int64_t nrows, int *tile_rows, int *nworkgroups, int64_t *pe
 int launch_zz_moments(const void *x, const SubView &sub, int64_t row0, int64_t nrows, void *partial, double *out,
                       hipStream_t st);
 
+// The Gram-matrix sweeps (gram_tile.h: GramPlan, the panel scheme).  A plan is host arithmetic from the subspace alone:
+// rows of A, tile rows of 16 of the result, the panel of 2^B rows a workgroup stages in LDS, the workgroups and the
+// panels each takes, and the bytes of LDS and of the partial tiles.
+struct GramPlan;
+
 // All <sigma+_i sigma-_j> of a state (pm_kernels.hip): P[i][j] = sum_r conj(A[r, i]) A[r, j], A[r, j] = x(r ^ e_j) on
-// the rows r whose bit j is set.  pm_plan is host arithmetic from the subspace alone (type DNM_FULL / DNM_PARITY /
-// DNM_SPIN_CONSERVE, L <= 64): rows of A, tile rows of 16 of the L x L result, the panel of 2^B rows a workgroup stages
-// in LDS, the workgroups and the panels each takes, and the bytes of LDS and of the partial tiles.
-struct PmPlan {
-  int32_t nb, B, nwg, K;          // tile rows, log2 of the panel's rows, workgroups, set bits of a row (SpinConserve)
-  int64_t nrows, npanels, per_wg;
-  size_t lds_bytes, table_bytes;  // dynamic LDS of a launch; of it the binomial table (SpinConserve)
-  size_t partial_bytes;           // nwg * (NT + nb^2) * 256 doubles, NT = nb (nb + 1) / 2
-};
-int pm_plan(int type, int L, int k, PmPlan *p);
+// the rows r whose bit j is set (type DNM_FULL / DNM_PARITY / DNM_SPIN_CONSERVE, L <= 64; L x L result).
+int pm_plan(int type, int L, int k, GramPlan *p);
 // x: the whole state (device; Full / Parity as it lies in the swizzled layout swz, SpinConserve in reference order);
 // nck: pm_binomials(L, K, L + 1) on the device (SpinConserve); partial: p.partial_bytes; out: L * L complex128 (device)
-int launch_pm_moments(const void *x, int type, int L, int k, int space, int swz, const PmPlan &p, const int64_t *nck,
+int launch_pm_moments(const void *x, int type, int L, int k, int space, int swz, const GramPlan &p, const int64_t *nck,
                       void *partial, void *out, hipStream_t st);
 
 // All bond-swap correlators of a state (swap_kernels.hip): G = A^H A, A[r, 0] = x(r), A[r, 1 + m] = x(r with the bits
 // of bond m exchanged) over the rows r of the subspace (xsec = +-1: the representatives of the XParity sector, type /
-// L / k the parent's).  swap_plan is host arithmetic: rows of A, tile rows of 16 of the (n + 1) x (n + 1) result, the
-// panel of 2^B rows, the workgroups -- a function of the rows alone -- and the bytes of LDS and of the partial tiles.
-struct SwapPlan {
-  int32_t nb, B, nwg, K;          // tile rows, log2 of the panel's rows, workgroups, set bits of a row (SpinConserve)
-  int64_t nrows, dim, npanels, per_wg;      // rows of the sweep; dimension of the (parent) subspace
-  size_t lds_bytes, table_bytes;  // dynamic LDS of a launch; of it the binomial table (SpinConserve)
-  size_t partial_bytes;           // nwg * (NT + nb^2) * 256 doubles, NT = nb (nb + 1) / 2
-};
-int swap_plan(int type, int L, int k, int nbonds, int xsec, SwapPlan *p);
+// L / k the parent's); (n + 1) x (n + 1) result, the workgroups a function of the rows alone.
+int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p);
 // x: the whole state (device; Full / Parity as it lies in the swizzled layout swz, SpinConserve in reference order);
 // bonds: 2 nbonds sites (host); nck: pm_binomials(L, k, L + 1) on the device (SpinConserve); partial: p.partial_bytes;
 // out: (nbonds + 1)^2 complex128 (device)
 int launch_swap_moments(const void *x, int type, int L, int space, int swz, int xsec, int nbonds, const int32_t *bonds,
-                        const SwapPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st);
+                        const GramPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st);
 
 // ---- vector kernels ---------------------------------------------------------
 int vk_set(void *x, int64_t n, double re, double im, hipStream_t st);

@@ -1,9 +1,7 @@
 // C ABI: device helpers, subspace maps, and the shell matrix (create / mult /
-// norm / diagonal / destroy).  See include/dynamite_amd.h for the reference
-// interfaces each entry point replaces.
+// norm / diagonal / destroy); the observables of a state are in observables.cpp.
+// See include/dynamite_amd.h for the reference interfaces each entry point replaces.
 #include "passes.h"
-#include "pm_rank.h"
-#include "swap_rank.h"
 #include "vec_api.h"
 #include "row_fused.h"
 
@@ -41,7 +39,7 @@ void DevBuf::release() {
   bytes = 0;
 }
 
-static int view_from_c(const dnm_subspace *s, SubView *v) {
+int view_from_c(const dnm_subspace *s, SubView *v) {
   DNM_CHECK(s != nullptr, "null subspace descriptor");
   DNM_CHECK(s->type >= DNM_FULL && s->type <= DNM_SPIN_CONSERVE, "unknown subspace type %d", s->type);
   DNM_CHECK(s->L >= 1 && s->L <= 63, "L=%lld out of range", (long long)s->L);
@@ -307,427 +305,6 @@ int dnm_check_conserves(int64_t nmasks, const int64_t *masks, const int64_t *mas
   int bad = 0;
   DNM_TRY(dnm_memcpy_d2h(&bad, dbad.p, sizeof(int), stream));
   *result = bad ? 0 : 1;
-  return 0;
-}
-
-// ---- reduced density matrix -----------------------------------------------------------
-static DevBuf g_rdm_scratch;     // released by dnm_release_workspace()
-}  // extern "C"
-namespace dnm {
-int rdm_release_scratch() {
-  g_rdm_scratch.release();
-  return 0;
-}
-}  // namespace dnm
-extern "C" {
-
-// runs of kept / traced spin positions (kernels.h: RdmGeom)
-static void rdm_geom(int L, int keep_size, const int64_t *keep, RdmGeom *out) {
-  RdmGeom &geo = *out;
-  memset(&geo, 0, sizeof(geo));
-  geo.k = keep_size;
-  geo.L = L;
-  uint64_t keepmask = 0;
-  for (int i = 0; i < keep_size; ++i) keepmask |= (uint64_t)1 << keep[i];
-  for (int pos = 0; pos < L;) {
-    const bool kept = (keepmask >> pos) & 1;
-    int end = pos;
-    while (end < L && (((keepmask >> end) & 1) != 0) == kept) ++end;
-    if (kept) {
-      geo.klen[geo.nseg_keep] = (int8_t)(end - pos);
-      geo.kpos[geo.nseg_keep++] = (int8_t)pos;
-    } else {
-      geo.tlen[geo.nseg_tr] = (int8_t)(end - pos);
-      geo.tpos[geo.nseg_tr++] = (int8_t)pos;
-    }
-    pos = end;
-  }
-}
-
-// the kept spins of a call: at most `cap` of them (over_cap: the caller's message, a format that is handed keep_size
-// twice and may use it once), inside [0, L), strictly increasing (bpetsc_template_1.c:117-121)
-static int rdm_check_keep(int L, int keep_size, const int64_t *keep, int cap, const char *over_cap) {
-  DNM_CHECK(keep_size <= L, "more kept spins than spins");
-  DNM_CHECK(keep_size <= cap, over_cap, keep_size, keep_size);
-  for (int i = 0; i < keep_size; ++i) {
-    DNM_CHECK(keep[i] >= 0 && keep[i] < L, "kept spin index %lld out of range [0, %d)", (long long)keep[i], L);
-    DNM_CHECK(i == 0 || keep[i] > keep[i - 1], "keep array must be strictly increasing");
-  }
-  return 0;
-}
-
-// Scratch for the partial tiles: up to 1 GiB it is kept between calls (hipMalloc costs more than the kernel), a larger
-// one lives in `big`, which the caller releases after the stream has drained.  `what`, tiles, tm, slices: for the
-// message when the device has no room.
-static int rdm_scratch(size_t bytes, DevBuf *big, void **scratch, const char *what, long long tiles, int tm,
-                       int slices) {
-  DevBuf &cached = g_rdm_scratch;
-  const bool keep_it = bytes <= ((size_t)1 << 30);
-  if (!keep_it || cached.bytes < bytes) {
-    if (keep_it) cached.release();
-    size_t free_b = 0, total_b = 0;
-    DNM_HIP(hipMemGetInfo(&free_b, &total_b));
-    DNM_CHECK(bytes <= free_b, "%s: %zu bytes of scratch asked for (%lld tiles of %d x %d in %d slices), %zu bytes of "
-              "device memory free", what, bytes, tiles, tm, tm, slices, free_b);
-    DNM_TRY((keep_it ? cached : *big).alloc(bytes));
-  }
-  *scratch = keep_it ? cached.p : big->p;
-  return 0;
-}
-
-int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
-                               void *rho, void *stream) {
-  DNM_CHECK(x && sub && rho && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
-  SubOwned s;
-  DNM_TRY(s.init(sub, true));
-  const int L = s.host.L;
-  DNM_TRY(rdm_check_keep(L, keep_size, keep, 15, "reduced density matrix of %d spins (4^%d entries) is too large"));
-  RdmGeom geo;
-  rdm_geom(L, keep_size, keep, &geo);
-  int logtm, ntiles, nsplit;
-  int64_t cps;
-  size_t pbytes;
-  rdm_plan(geo, &logtm, &ntiles, &nsplit, &cps, &pbytes);
-  DevBuf big;
-  void *scratch = nullptr;
-  DNM_TRY(rdm_scratch(pbytes, &big, &scratch, "reduced density matrix", ntiles, 1 << logtm, nsplit));
-  DNM_TRY(launch_rdm(x, s.dev, geo, scratch, rho, S(stream)));
-  DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` is released on return
-  return 0;
-}
-
-// ---- sector-resolved reduced density matrix (SpinConserve, XParity over SpinConserve) ------------------------------
-// argument checks and the list of feasible blocks, on the host
-static int rdm_sector_blocks_of(const dnm_subspace *sub, int keep_size, const int64_t *keep, int xparity_sector,
-                                SubView *view, RdmGeom *geo, bool *contig, std::vector<RdmSectorBlock> *blocks) {
-  DNM_CHECK(sub && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
-  SubView v{};
-  DNM_TRY(view_from_c(sub, &v));
-  DNM_CHECK(v.type == DNM_SPIN_CONSERVE, "sector-resolved reduced density matrices need a SpinConserve subspace "
-            "(type %d given)", v.type);
-  const int L = v.L, k = v.k;
-  DNM_CHECK(xparity_sector == 0 || xparity_sector == 1 || xparity_sector == -1, "xparity_sector must be 0, +1 or -1");
-  DNM_CHECK(xparity_sector == 0 || L == 2 * k, "XParity needs SpinConserve(L, L/2): L=%d, k=%d", L, k);
-  DNM_TRY(rdm_check_keep(L, keep_size, keep, 40, "reduced density matrix blocks of %d kept spins: at most 40"));
-  rdm_geom(L, keep_size, keep, geo);
-  // the kept spins are [0, keep_size): increasing from 0 and ending at keep_size - 1
-  *contig = keep_size < L && (keep_size == 0 || keep[keep_size - 1] == keep_size - 1);
-  *view = v;
-  blocks->clear();
-  const int nlo = std::max(0, k - (L - keep_size)), nhi = std::min(k, keep_size);
-  for (int n = nlo; n <= nhi; ++n) {
-    RdmSectorBlock b{};
-    b.n = n;
-    b.m = k - n;
-    b.dim = v.nchoosek[(int64_t)n * v.ld + keep_size];
-    b.traced = v.nchoosek[(int64_t)(k - n) * v.ld + (L - keep_size)];
-    DNM_CHECK(b.dim >= 1 && b.dim < ((int64_t)1 << 31), "block n=%d of the reduced density matrix has %lld rows: "
-              "2^31 or more", n, (long long)b.dim);
-    blocks->push_back(b);
-  }
-  return 0;
-}
-
-int dnm_rdm_sector_plan(const dnm_subspace *sub, int keep_size, const int64_t *keep, int xparity_sector, int *nblocks,
-                        int32_t *n_of_block, int64_t *dim_of_block, int64_t *traced_of_block,
-                        size_t *scratch_bytes_max) {
-  DNM_CHECK(nblocks, "null argument");
-  SubView v{};
-  RdmGeom geo;
-  bool contig;
-  std::vector<RdmSectorBlock> blocks;
-  DNM_TRY(rdm_sector_blocks_of(sub, keep_size, keep, xparity_sector, &v, &geo, &contig, &blocks));
-  *nblocks = (int)blocks.size();
-  for (size_t i = 0; i < blocks.size(); ++i) {
-    if (n_of_block) n_of_block[i] = blocks[i].n;
-    if (dim_of_block) dim_of_block[i] = blocks[i].dim;
-    if (traced_of_block) traced_of_block[i] = blocks[i].traced;
-  }
-  if (scratch_bytes_max) {
-    int64_t nt;
-    int ns;
-    size_t tb, pb;
-    DNM_TRY(rdm_sector_plan((int)blocks.size(), blocks.data(), &nt, &ns, &tb, &pb));
-    *scratch_bytes_max = tb + pb;
-  }
-  return 0;
-}
-
-int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
-                          int xparity_sector, int nsel, const int32_t *sel_n, void *const *out_ptrs, void *stream) {
-  DNM_CHECK(x && nsel >= 1 && sel_n && out_ptrs, "null argument");
-  SubView v{};
-  RdmGeom geo;
-  bool contig;
-  std::vector<RdmSectorBlock> all, blocks;
-  DNM_TRY(rdm_sector_blocks_of(sub, keep_size, keep, xparity_sector, &v, &geo, &contig, &all));
-  DNM_CHECK(v.sc3 == 0, "the sector kernels read the state in reference order (vec_swizzle %d given)", v.sc3);
-  for (int i = 0; i < nsel; ++i) {
-    const int n = sel_n[i] - all.front().n;
-    DNM_CHECK(n >= 0 && n < (int)all.size(), "no block with %d set bits among the kept spins (feasible: %d..%d)",
-              (int)sel_n[i], all.front().n, all.back().n);
-    DNM_CHECK(out_ptrs[i], "null output for block n=%d", (int)sel_n[i]);
-    blocks.push_back(all[(size_t)n]);
-    blocks.back().out = out_ptrs[i];
-  }
-  int64_t ntiles;
-  int nsplit;
-  size_t tbytes, pbytes;
-  DNM_TRY(rdm_sector_plan((int)blocks.size(), blocks.data(), &ntiles, &nsplit, &tbytes, &pbytes));
-  const size_t bytes = tbytes + pbytes;
-  SubOwned s;
-  DNM_TRY(s.init(sub, true));
-  DevBuf big;
-  void *scratch = nullptr;
-  DNM_TRY(rdm_scratch(bytes, &big, &scratch, "reduced density matrix blocks", (long long)ntiles, 64, nsplit));
-  DNM_TRY(launch_rdm_sector(x, s.dev, geo, contig, xparity_sector, (int)blocks.size(), blocks.data(), ntiles, nsplit,
-                            tbytes, scratch, S(stream)));
-  DNM_HIP(hipStreamSynchronize(S(stream)));     // `big` and the subspace tables are released on return
-  return 0;
-}
-
-// ---- first and second sigma-z moments -----------------------------------------------------------------------------
-// what the plan and the call check alike: the descriptor, the layout and the rows
-static int zz_check(const dnm_subspace *sub, int64_t row0, int64_t nrows, SubView *v) {
-  DNM_CHECK(sub, "null argument");
-  DNM_TRY(view_from_c(sub, v));
-  DNM_CHECK(v->sc3 == 0, "sigma-z moments read a SpinConserve state in reference order (vec_swizzle %d given: "
-            "dnm_vec_layout_copy converts)", v->sc3);
-  DNM_CHECK(sub->site_perm == nullptr, "sigma-z moments take no relabelled subspace (site_perm given): hand over the "
-            "state in reference order with a descriptor without it");
-  const int64_t dim = sub_dim(*v);
-  DNM_CHECK(nrows >= 0 && row0 >= 0 && nrows <= dim && row0 <= dim - nrows,
-            "rows [%lld, %lld + %lld) of a subspace of dimension %lld", (long long)row0, (long long)row0,
-            (long long)nrows, (long long)dim);
-  const int64_t run = (int64_t)1 << v->swz;
-  DNM_CHECK(v->swz == 0 || nrows <= run || nrows % run == 0, "a block of %lld rows has no layout of swizzle shift %d: "
-            "beyond 2^%d rows the size must be a multiple of 2^%d", (long long)nrows, v->swz, v->swz, v->swz);
-  return 0;
-}
-
-int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
-                        size_t *scratch_bytes) {
-  SubView v{};
-  DNM_TRY(zz_check(sub, 0, nrows, &v));
-  int nb, nwg;
-  int64_t per_wg;
-  size_t bytes;
-  zz_plan(v.L, nrows, &nb, &nwg, &per_wg, &bytes);
-  if (tile_rows) *tile_rows = nb;
-  if (nworkgroups) *nworkgroups = nwg;
-  if (scratch_bytes) *scratch_bytes = bytes;
-  return 0;
-}
-
-int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream) {
-  DNM_CHECK(out && (x || nrows == 0), "null argument");
-  SubView v{};
-  DNM_TRY(zz_check(sub, row0, nrows, &v));
-  int nb, nwg;
-  int64_t per_wg;
-  size_t pbytes;
-  zz_plan(v.L, nrows, &nb, &nwg, &per_wg, &pbytes);
-  const size_t D = (size_t)v.L + 1;
-  SubOwned s;
-  DNM_TRY(s.init(sub, true));
-  DevBuf big;
-  void *scratch = nullptr;       // the partial tiles, then the matrix
-  DNM_TRY(rdm_scratch(pbytes + D * D * sizeof(double), &big, &scratch, "sigma-z moments", (long long)(nb * (nb + 1) / 2),
-                      16, nwg));
-  double *m_dev = (double *)((char *)scratch + pbytes);
-  DNM_TRY(launch_zz_moments(x, s.dev, row0, nrows, scratch, m_dev, S(stream)));
-  // (synchronises: the subspace tables are released on return)
-  return dnm_memcpy_d2h(out, m_dev, D * D * sizeof(double), stream);
-}
-
-// ---- sigma+ sigma- moments ----------------------------------------------------------------------------------------
-// what the plan, the call and the partner table check alike, before any device call.  The pass brings its own
-// binomials (sector k + 1), so that the descriptor's fields are read here and nothing else of it is used.
-static int pm_check(const dnm_subspace *sub, const char *what) {
-  DNM_CHECK(sub, "%s: null subspace descriptor", what);
-  DNM_CHECK(sub->type != DNM_EXPLICIT, "%s: Explicit subspaces are not supported (the partners of a row have no "
-            "closed-form index there)", what);
-  DNM_CHECK(sub->type == DNM_FULL || sub->type == DNM_PARITY || sub->type == DNM_SPIN_CONSERVE,
-            "%s: unknown subspace type %d", what, sub->type);
-  DNM_CHECK(sub->L >= 1 && sub->L <= 64, "%s: L=%lld out of range (at most 64 spins)", what, (long long)sub->L);
-  if (sub->type == DNM_SPIN_CONSERVE) {
-    DNM_CHECK(sub->k >= 0 && sub->k <= sub->L, "%s: bad SpinConserve descriptor (k=%lld)", what, (long long)sub->k);
-    DNM_CHECK(sub->vec_swizzle == 0, "%s: a SpinConserve state is read in reference order (vec_swizzle %d given: "
-              "dnm_vec_layout_copy converts)", what, sub->vec_swizzle);
-    DNM_CHECK(sub->site_perm == nullptr, "%s: no relabelled subspace (site_perm given): hand over the state in "
-              "reference order with a descriptor without it", what);
-  } else {
-    DNM_CHECK(sub->site_perm == nullptr, "%s: site_perm given for a subspace that is not SpinConserve", what);
-    DNM_CHECK(sub->vec_swizzle == 0 || (sub->vec_swizzle >= 5 && sub->vec_swizzle <= 24),
-              "%s: vec_swizzle %d: the shift of a swizzled vector lies in [5, 24]", what, sub->vec_swizzle);
-    if (sub->type == DNM_PARITY) DNM_CHECK(sub->space == 0 || sub->space == 1, "%s: parity space must be 0 or 1", what);
-  }
-  return 0;
-}
-
-int dnm_pm_moments_plan(const dnm_subspace *sub, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
-                        size_t *lds_bytes, size_t *scratch_bytes) {
-  DNM_TRY(pm_check(sub, "sigma+ sigma- moments"));
-  PmPlan p;
-  DNM_TRY(pm_plan(sub->type, (int)sub->L, (int)sub->k, &p));
-  if (tile_rows) *tile_rows = p.nb;
-  if (panel_rows_log2) *panel_rows_log2 = p.B;
-  if (nworkgroups) *nworkgroups = p.nwg;
-  if (lds_bytes) *lds_bytes = p.lds_bytes;
-  if (scratch_bytes) *scratch_bytes = p.partial_bytes;
-  return 0;
-}
-
-int dnm_pm_moments(const void *x, const dnm_subspace *sub, double *out, void *stream) {
-  DNM_CHECK(x && out, "sigma+ sigma- moments: null argument");
-  DNM_TRY(pm_check(sub, "sigma+ sigma- moments"));
-  const int L = (int)sub->L;
-  PmPlan p;
-  DNM_TRY(pm_plan(sub->type, L, (int)sub->k, &p));
-  const size_t obytes = (size_t)L * (size_t)L * 2 * sizeof(double);
-  if (p.nrows == 0) {       // SpinConserve(L, L): no configuration has a spin left to lower
-    memset(out, 0, obytes);
-    return 0;
-  }
-  std::vector<int64_t> nck;
-  if (sub->type == DNM_SPIN_CONSERVE) {
-    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
-    pm_binomials(L, p.K, L + 1, nck.data());
-  }
-  DevBuf big;
-  void *scratch = nullptr;       // the partial tiles, the matrix, the binomials
-  DNM_TRY(rdm_scratch(p.partial_bytes + obytes + p.table_bytes, &big, &scratch, "sigma+ sigma- moments",
-                      (long long)(p.partial_bytes / 2048 / (size_t)p.nwg), 16, p.nwg));
-  void *p_dev = (char *)scratch + p.partial_bytes;
-  int64_t *t_dev = (int64_t *)((char *)p_dev + obytes);
-  if (!nck.empty())
-    DNM_HIP(hipMemcpyAsync(t_dev, nck.data(), nck.size() * sizeof(int64_t), hipMemcpyHostToDevice, S(stream)));
-  DNM_TRY(launch_pm_moments(x, sub->type, L, (int)sub->k, (int)sub->space, sub->vec_swizzle, p, t_dev, scratch, p_dev,
-                            S(stream)));
-  // (synchronises: `big` and the host table are released on return)
-  return dnm_memcpy_d2h(out, p_dev, obytes, stream);
-}
-
-int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *rows, int64_t *out) {
-  DNM_TRY(pm_check(sub, "sigma+ sigma- partner indices"));
-  DNM_CHECK(sub->type == DNM_SPIN_CONSERVE, "sigma+ sigma- partner indices: SpinConserve only (Full and Parity "
-            "partners are index ^ mask)");
-  DNM_CHECK(n >= 0 && (n == 0 || (rows && out)), "sigma+ sigma- partner indices: null argument");
-  const int L = (int)sub->L;
-  PmPlan p;
-  DNM_TRY(pm_plan(sub->type, L, (int)sub->k, &p));
-  std::vector<int64_t> nck((size_t)(p.K + 1) * (size_t)(L + 1));
-  if (p.nrows) pm_binomials(L, p.K, L + 1, nck.data());
-  for (int64_t i = 0; i < n; ++i) {
-    DNM_CHECK(rows[i] >= 0 && rows[i] < p.nrows, "sigma+ sigma- partner indices: row %lld of a sector of %lld rows "
-              "(%d set bits)", (long long)rows[i], (long long)p.nrows, p.K);
-    int64_t *o = out + i * L;
-    for (int j = 0; j < L; ++j) o[j] = -1;
-    pm_partners(pm_unrank(rows[i], L, p.K, nck.data(), L + 1), nck.data(), L + 1,
-                [&](int j, int64_t idx) { o[j] = idx; });
-  }
-  return 0;
-}
-
-// ---- bond-swap moments --------------------------------------------------------------------------------------------
-// what the plan, the call and the partner table check alike, before any device call (bonds: null for the plan)
-static int swap_check(const dnm_subspace *sub, int xsec, int nbonds, const int32_t *bonds) {
-  const char *what = "bond-swap moments";
-  DNM_TRY(pm_check(sub, what));
-  DNM_CHECK(xsec == 0 || xsec == 1 || xsec == -1, "%s: xparity_sector %d (0, +1 or -1)", what, xsec);
-  if (xsec != 0) {
-    DNM_CHECK(sub->L >= 2, "%s: an XParity sector of L=%lld", what, (long long)sub->L);
-    if (sub->type == DNM_PARITY)
-      DNM_CHECK(sub->L % 2 == 0, "%s: Parity carries the global flip of XParity only when L is even (L=%lld)", what,
-                (long long)sub->L);
-    if (sub->type == DNM_SPIN_CONSERVE)
-      DNM_CHECK(sub->L == 2 * sub->k, "%s: SpinConserve carries the global flip of XParity only when k = L / 2 "
-                "(L=%lld, k=%lld)", what, (long long)sub->L, (long long)sub->k);
-  }
-  DNM_CHECK(nbonds >= 1 && nbonds <= 63, "%s: %d bonds (1 to 63 in one call)", what, nbonds);
-  for (int m = 0; bonds && m < nbonds; ++m) {
-    const int a = bonds[2 * m], b = bonds[2 * m + 1];
-    DNM_CHECK(a >= 0 && a < sub->L && b >= 0 && b < sub->L, "%s: bond %d = (%d, %d) has a site outside [0, %lld)", what,
-              m, a, b, (long long)sub->L);
-    DNM_CHECK(a != b, "%s: bond %d joins site %d to itself", what, m, a);
-  }
-  return 0;
-}
-
-int dnm_swap_moments_plan(const dnm_subspace *sub, int nbonds, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
-                          size_t *lds_bytes, size_t *scratch_bytes) {
-  DNM_TRY(swap_check(sub, 0, nbonds, nullptr));
-  SwapPlan p;
-  DNM_TRY(swap_plan(sub->type, (int)sub->L, (int)sub->k, nbonds, 0, &p));
-  if (tile_rows) *tile_rows = p.nb;
-  if (panel_rows_log2) *panel_rows_log2 = p.B;
-  if (nworkgroups) *nworkgroups = p.nwg;
-  if (lds_bytes) *lds_bytes = p.lds_bytes;
-  if (scratch_bytes) *scratch_bytes = p.partial_bytes;
-  return 0;
-}
-
-int dnm_swap_moments(const void *x, const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds,
-                     double *out, void *stream) {
-  DNM_CHECK(x && out && bonds, "bond-swap moments: null argument");
-  DNM_TRY(swap_check(sub, xparity_sector, nbonds, bonds));
-  const int L = (int)sub->L;
-  SwapPlan p;
-  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, nbonds, xparity_sector, &p));
-  const size_t D = (size_t)nbonds + 1, obytes = D * D * 2 * sizeof(double);
-  std::vector<int64_t> nck;
-  if (sub->type == DNM_SPIN_CONSERVE) {
-    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
-    pm_binomials(L, p.K, L + 1, nck.data());
-  }
-  DevBuf big;
-  void *scratch = nullptr;       // the partial tiles, the matrix, the binomials
-  DNM_TRY(rdm_scratch(p.partial_bytes + obytes + p.table_bytes, &big, &scratch, "bond-swap moments",
-                      (long long)(p.partial_bytes / 2048 / (size_t)p.nwg), 16, p.nwg));
-  void *g_dev = (char *)scratch + p.partial_bytes;
-  int64_t *t_dev = (int64_t *)((char *)g_dev + obytes);
-  if (!nck.empty())
-    DNM_HIP(hipMemcpyAsync(t_dev, nck.data(), nck.size() * sizeof(int64_t), hipMemcpyHostToDevice, S(stream)));
-  DNM_TRY(launch_swap_moments(x, sub->type, L, (int)sub->space, sub->vec_swizzle, xparity_sector, nbonds, bonds, p,
-                              t_dev, scratch, g_dev, S(stream)));
-  // (synchronises: `big` and the host table are released on return)
-  return dnm_memcpy_d2h(out, g_dev, obytes, stream);
-}
-
-int dnm_swap_partner_indices(const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds, int64_t n,
-                             const int64_t *rows, int64_t *idx, int8_t *sign) {
-  DNM_CHECK(bonds, "bond-swap partner indices: null argument");
-  DNM_TRY(swap_check(sub, xparity_sector, nbonds, bonds));
-  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "bond-swap partner indices: null argument");
-  const int L = (int)sub->L;
-  SwapPlan p;
-  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, nbonds, xparity_sector, &p));
-  const bool sc = sub->type == DNM_SPIN_CONSERVE, parity = sub->type == DNM_PARITY;
-  std::vector<int64_t> nck;
-  if (sc) {
-    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
-    pm_binomials(L, p.K, L + 1, nck.data());
-  }
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t row = rows[i];
-    DNM_CHECK(row >= 0 && row < p.nrows, "bond-swap partner indices: row %lld of %lld rows", (long long)row,
-              (long long)p.nrows);
-    const uint64_t cfg = sc ? pm_unrank(row, L, p.K, nck.data(), L + 1)
-                         : parity ? ((uint64_t)row << 1) | (uint64_t)(hd_par((uint64_t)row) ^ (int)sub->space)
-                                  : (uint64_t)row;
-    for (int m = 0; m < nbonds; ++m) {
-      const int a = bonds[2 * m], b = bonds[2 * m + 1];
-      int fl = 0;
-      int64_t at = row;
-      if (sc) {
-        at = swap_sc_partner(cfg, row, a, b, L, p.dim, xparity_sector, nck.data(), L + 1, &fl);
-      } else if (((cfg >> a) ^ (cfg >> b)) & 1) {
-        at = row ^ (int64_t)swap_index_mask(parity, L, a, b, xparity_sector, &fl);
-      }
-      idx[i * nbonds + m] = at;
-      sign[i * nbonds + m] = (int8_t)(fl ? xparity_sector : 1);
-    }
-  }
   return 0;
 }
 

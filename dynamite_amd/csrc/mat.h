@@ -21,6 +21,8 @@ struct SubOwned {
   DevBuf d_nck, d_smap, d_rind, d_rstates, d_bucket;
   int init(const dnm_subspace *s, bool want_device);
 };
+// the checked view of a caller's descriptor: its tables stay the caller's (mat.cpp)
+int view_from_c(const dnm_subspace *s, SubView *v);
 
 // What one launch of the tiled kernel reads, as passes.cpp builds it on the host
 struct PassRecords {

@@ -26,57 +26,41 @@
 // No atomics: the wavefronts are summed through LDS in a fixed order, the workgroups by pm_finalize_kernel in a fixed
 // order, which forms Q - Q^T, mirrors the lower triangle as the conjugate and writes real diagonals.  The number of
 // workgroups follows from the number of rows alone: two calls return the same bits on any device.
-#include "rdm_tile.h"
+#include "gram_tile.h"
 #include "pm_rank.h"
 
 namespace dnm {
 
-constexpr int PM_NT = 256;                      // threads of a workgroup: four wavefronts, one per SIMD
-constexpr int64_t PM_MAX_WG = 1024;
-constexpr size_t PM_LDS_BUDGET = 152 * 1024;    // of the 160 KB of a CU
 // log2 of the panel's rows: the largest that fits, but 2^7 from two tile rows on -- two workgroups then share a compute
 // unit and one fills its panel while the other multiplies.  Measured at NB = 2 on MI355X, Full L=30 / SpinConserve(32,
 // 16): 2^8 rows 302.9 / 174.7 ms, 2^7 273.9 / 155.1 ms, 2^6 437.9 / 260.3 ms.  One tile row (L <= 16) is not measured
 // and keeps the largest panel.
 constexpr int PM_B_MAX = 9, PM_B_MAX_WIDE = 7, PM_B_MIN = 6;
 
-static inline int pm_nacc(int nb) { return nb * (nb + 1) / 2 + nb * nb; }
-
-int pm_plan(int type, int L, int k, PmPlan *p) {
-  PmPlan q{};
-  q.nb = (L + 15) / 16;
+// rows: every configuration (the opposite parity), or sector K = k + 1 with its binomials -- none where it is empty; a
+// workgroup per panel
+int pm_plan(int type, int L, int k, GramPlan *p) {
+  GramPlan q{};
   q.K = k + 1;
+  int64_t nrows;
+  size_t table_bytes = 0;
   if (type == DNM_SPIN_CONSERVE) {
     std::vector<int64_t> t((size_t)(L + 1) * (size_t)(L + 1));
     pm_binomials(L, L, L + 1, t.data());
-    q.nrows = q.K <= L ? t[(size_t)q.K * (L + 1) + L] : 0;
-    q.table_bytes = q.nrows ? (size_t)(q.K + 1) * (size_t)(L + 1) * sizeof(int64_t) : 0;
+    nrows = q.K <= L ? t[(size_t)q.K * (L + 1) + L] : 0;
+    if (nrows) table_bytes = (size_t)(q.K + 1) * (size_t)(L + 1) * sizeof(int64_t);
   } else {
     if (L - (type == DNM_PARITY) > 62) {
       set_error("sigma+ sigma- moments: 2^%d rows", L - (type == DNM_PARITY));
       return 1;
     }
-    q.nrows = (int64_t)1 << (L - (type == DNM_PARITY));
+    nrows = (int64_t)1 << (L - (type == DNM_PARITY));
   }
-  const size_t row_bytes = (size_t)(16 * q.nb + 1) * 16;
-  q.B = q.nb == 1 ? PM_B_MAX : PM_B_MAX_WIDE;
-  if (const char *e = knob("DNM_PM_B")) {       // experiments: other panels
-    const int b = atoi(e);
-    if (b >= PM_B_MIN && b <= PM_B_MAX) q.B = b;
-  }
-  while (q.B > PM_B_MIN && (row_bytes << q.B) + q.table_bytes > PM_LDS_BUDGET) --q.B;
-  q.lds_bytes = (row_bytes << q.B) + q.table_bytes;
-  // (the reduction buffer of the wavefronts' sum takes the panel's place after the sweep)
-  if (q.lds_bytes > PM_LDS_BUDGET || (size_t)pm_nacc(q.nb) * 256 * sizeof(double) > (row_bytes << q.B)) {
+  const char *e = knob("DNM_PM_B");             // experiments: other panels
+  if (!gram_plan(L, nrows, table_bytes, PM_B_MAX, PM_B_MAX_WIDE, PM_B_MIN, e ? atoi(e) : 0, PM_MAX_WG, &q)) {
     set_error("internal: sigma+ sigma- panel of %zu bytes", q.lds_bytes);
     return 1;
   }
-  q.npanels = (q.nrows + ((int64_t)1 << q.B) - 1) >> q.B;
-  int64_t nwg = q.npanels < PM_MAX_WG ? q.npanels : PM_MAX_WG;
-  if (nwg < 1) nwg = 1;
-  q.nwg = (int)nwg;
-  q.per_wg = (q.npanels + nwg - 1) / nwg;
-  q.partial_bytes = (size_t)nwg * (size_t)pm_nacc(q.nb) * 256 * sizeof(double);
   *p = q;
   return 0;
 }
@@ -148,102 +132,20 @@ pm_moments_kernel(const c128 *__restrict__ x, const PmArgs a, const int64_t *__r
       }
     }
     __syncthreads();
-    for (int q = wave; q < rows / 4; q += PM_NT / 64) {
-      const c128 *pr = panel + (4 * q + slot) * LDP + r;
-      c128 v[NB];
-#pragma unroll
-      for (int t = 0; t < NB; ++t) v[t] = pr[16 * t];
-#pragma unroll
-      for (int ti = 0; ti < NB; ++ti)
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj) {
-          const int i = ti * (ti + 1) / 2 + tj;
-          acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].x, v[tj].x, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].y, v[tj].y, acc[i], 0, 0, 0);
-        }
-#pragma unroll
-      for (int ti = 0; ti < NB; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < NB; ++tj) {
-          const int i = NTILE + ti * NB + tj;
-          acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].x, v[tj].y, acc[i], 0, 0, 0);
-        }
-    }
+    pm_tile_multiply<NB>(panel, rows, wave, slot, r, acc);
     __syncthreads();
   }
 
-  // the four wavefronts, summed in the order ((0 + 1) + 2) + 3 through the panel's LDS; C/D layout: col = lane & 15,
-  // row = (lane >> 4) + 4 * reg
-  double *red = reinterpret_cast<double *>(pm_lds);
-  for (int wv = 1; wv < PM_NT / 64; ++wv) {
-    __syncthreads();
-    if (wave == wv) {
-#pragma unroll
-      for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) red[i * 256 + (slot + 4 * gq) * 16 + r] = acc[i][gq];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) acc[i][gq] += red[i * 256 + (slot + 4 * gq) * 16 + r];
-    }
-  }
-  if (wave == 0) {
-    double *out = partial + (int64_t)blockIdx.x * (NACC * 256);
-#pragma unroll
-    for (int i = 0; i < NACC; ++i)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) out[i * 256 + (slot + 4 * gq) * 16 + r] = acc[i][gq];
-  }
+  pm_tile_reduce_store<NACC>(reinterpret_cast<double *>(pm_lds), wave, slot, r, acc,
+                             partial + (int64_t)blockIdx.x * (NACC * 256));
 }
 
-// P (L x L complex128, row-major) from the workgroups' partial tiles, summed in their order: entry (a, b), b <= a, is
-// (Re[a][b], Q[a][b] - Q[b][a]); the upper triangle is its conjugate and the diagonal real.  One workgroup per
-// lower-triangle tile.
 __global__ void __launch_bounds__(PM_NT)
 pm_finalize_kernel(const double *__restrict__ partial, int nwg, int nb, int L, c128 *__restrict__ out) {
-  int ti, tj;
-  rdm_tile_coords(blockIdx.x, &ti, &tj);
-  const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
-  const int a = ti * 16 + row, b = tj * 16 + col;
-  if (a >= L || b >= L || b > a) return;
-  const int ntile = nb * (nb + 1) / 2, nacc = ntile + nb * nb;
-  const int64_t e_re = (int64_t)blockIdx.x * 256 + row * 16 + col;
-  const int64_t e_ab = (int64_t)(ntile + ti * nb + tj) * 256 + row * 16 + col;
-  const int64_t e_ba = (int64_t)(ntile + tj * nb + ti) * 256 + col * 16 + row;
-  double re = 0.0, qab = 0.0, qba = 0.0;
-  for (int g = 0; g < nwg; ++g) {
-    const double *p = partial + (int64_t)g * nacc * 256;
-    re += p[e_re];
-    qab += p[e_ab];
-    qba += p[e_ba];
-  }
-  const double im = a == b ? 0.0 : qab - qba;
-  out[a * L + b] = make_double2(re, im);
-  if (a != b) out[b * L + a] = make_double2(re, -im);
+  pm_tile_finalize(partial, nwg, nb, L, out);
 }
 
-template <int TYPE>
-static int pm_launch_nb(const PmPlan &p, const c128 *x, const PmArgs &a, const int64_t *nck, double *partial,
-                        hipStream_t st) {
-  void (*k)(const c128 *, const PmArgs, const int64_t *, double *) = nullptr;
-  switch (p.nb) {
-    case 1: k = pm_moments_kernel<TYPE, 1>; break;
-    case 2: k = pm_moments_kernel<TYPE, 2>; break;
-    case 3: k = pm_moments_kernel<TYPE, 3>; break;
-    case 4: k = pm_moments_kernel<TYPE, 4>; break;
-    default: set_error("internal: %d tile rows of sigma+ sigma- moments", p.nb); return 1;
-  }
-  DNM_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  hipLaunchKernelGGL(k, dim3((unsigned)p.nwg), dim3(PM_NT), p.lds_bytes, st, x, a, nck, partial);
-  DNM_HIP(hipGetLastError());
-  return 0;
-}
-
-int launch_pm_moments(const void *x, int type, int L, int k, int space, int swz, const PmPlan &p, const int64_t *nck,
+int launch_pm_moments(const void *x, int type, int L, int k, int space, int swz, const GramPlan &p, const int64_t *nck,
                       void *partial, void *out, hipStream_t st) {
   PmArgs a{};
   a.nrows = p.nrows;
@@ -262,12 +164,14 @@ int launch_pm_moments(const void *x, int type, int L, int k, int space, int swz,
   }
   const c128 *xp = (const c128 *)x;
   double *pp = (double *)partial;
-  switch (type) {
-    case DNM_FULL: DNM_TRY(pm_launch_nb<DNM_FULL>(p, xp, a, nck, pp, st)); break;
-    case DNM_PARITY: DNM_TRY(pm_launch_nb<DNM_PARITY>(p, xp, a, nck, pp, st)); break;
-    case DNM_SPIN_CONSERVE: DNM_TRY(pm_launch_nb<DNM_SPIN_CONSERVE>(p, xp, a, nck, pp, st)); break;
-    default: set_error("sigma+ sigma- moments: subspace type %d", type); return 1;
-  }
+  DNM_TRY(gram_dispatch<false>(type, p.nb, "sigma+ sigma- moments", "sigma+ sigma- moments: subspace type %d",
+                               [&](auto T, auto NB) {
+    auto k = pm_moments_kernel<decltype(T)::value, decltype(NB)::value>;
+    DNM_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL(k, dim3((unsigned)p.nwg), dim3(PM_NT), p.lds_bytes, st, xp, a, nck, pp);
+    DNM_HIP(hipGetLastError());
+    return 0;
+  }));
   hipLaunchKernelGGL(pm_finalize_kernel, dim3((unsigned)(p.nb * (p.nb + 1) / 2)), dim3(PM_NT), 0, st,
                      (const double *)pp, p.nwg, p.nb, L, (c128 *)out);
   DNM_HIP(hipGetLastError());

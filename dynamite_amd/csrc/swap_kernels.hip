@@ -2,7 +2,7 @@
 // the spins a and b, so with the operand matrix over the rows r of the subspace
 //   A[r, 0] = psi(r),   A[r, 1 + m] = psi(r with bits a_m and b_m exchanged)
 // the Gram matrix G = A^H A ((n + 1) x (n + 1) complex128, Hermitian) holds G[0][0] = <psi|psi>, G[0][1 + m] = <P_m> and
-// G[1 + m][1 + m'] = <P_m P_m'>: the Hermitian rank-N update of pm_tile.h on v_mfma_f64_16x16x4_f64, NB = ceil((n + 1)
+// G[1 + m][1 + m'] = <P_m P_m'>: the Hermitian rank-N update of gram_tile.h on v_mfma_f64_16x16x4_f64, NB = ceil((n + 1)
 // / 16) <= 4 tile rows.  A swap keeps a row inside Full, Parity and SpinConserve -- the rows are the subspace's own --
 // and commutes with the global flip: for a state on an XParity sector s the rows are the representatives (the parent's
 // first dim / 2 rows, bit L - 1 clear) and a partner whose bit L - 1 is set is s times the amplitude of its complement;
@@ -17,9 +17,9 @@
 // SpinConserve: reference order.  A thread unranks its row (binomials in LDS) and ranks each swapped configuration by
 // swap_rank.h's difference form; under XParity a partner with bit L - 1 set is fetched at dim - 1 - rank.
 //
-// No atomics: wavefronts and workgroups are summed in a fixed order (pm_tile.h).  The number of workgroups follows from
+// No atomics: wavefronts and workgroups are summed in a fixed order (gram_tile.h).  The number of workgroups follows from
 // the number of rows alone: two calls return the same bits on any device.
-#include "pm_tile.h"
+#include "gram_tile.h"
 #include "swap_rank.h"
 
 namespace dnm {
@@ -29,15 +29,18 @@ namespace dnm {
 constexpr int SWAP_B_MAX = 9, SWAP_B_MAX_WIDE = 7, SWAP_B_MIN = 6;
 constexpr int SWAP_ROWS_PER_WG_LOG2 = 9;        // workgroups = ceil(rows / 2^9), at most PM_MAX_WG
 
-int swap_plan(int type, int L, int k, int nbonds, int xsec, SwapPlan *p) {
-  SwapPlan q{};
-  q.nb = (nbonds + 1 + 15) / 16;
+static_assert(SWAP_B_MAX <= SWAP_ROWS_PER_WG_LOG2, "a workgroup has at least one panel");
+
+// rows: the subspace's own (the representatives of an XParity sector), with the binomials of sector K = k
+int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p) {
+  GramPlan q{};
   q.K = type == DNM_SPIN_CONSERVE ? k : 0;
+  size_t table_bytes = 0;
   if (type == DNM_SPIN_CONSERVE) {
     std::vector<int64_t> t((size_t)(k + 1) * (size_t)(L + 1));
     pm_binomials(L, k, L + 1, t.data());
     q.dim = t[(size_t)k * (L + 1) + L];
-    q.table_bytes = t.size() * sizeof(int64_t);
+    table_bytes = t.size() * sizeof(int64_t);
   } else {
     if (L - (type == DNM_PARITY) > 62) {
       set_error("bond-swap moments: 2^%d rows", L - (type == DNM_PARITY));
@@ -45,23 +48,12 @@ int swap_plan(int type, int L, int k, int nbonds, int xsec, SwapPlan *p) {
     }
     q.dim = (int64_t)1 << (L - (type == DNM_PARITY));
   }
-  q.nrows = xsec ? q.dim / 2 : q.dim;
-  const size_t row_bytes = (size_t)(16 * q.nb + 1) * 16;
-  q.B = q.nb == 1 ? SWAP_B_MAX : SWAP_B_MAX_WIDE;
-  while (q.B > SWAP_B_MIN && (row_bytes << q.B) + q.table_bytes > PM_LDS_BUDGET) --q.B;
-  q.lds_bytes = (row_bytes << q.B) + q.table_bytes;
-  // (the reduction buffer of the wavefronts' sum takes the panel's place after the sweep)
-  if (q.lds_bytes > PM_LDS_BUDGET || (size_t)pm_nacc(q.nb) * 256 * sizeof(double) > (row_bytes << q.B)) {
+  const int64_t nrows = xsec ? q.dim / 2 : q.dim;
+  const int64_t nwg = (nrows + ((int64_t)1 << SWAP_ROWS_PER_WG_LOG2) - 1) >> SWAP_ROWS_PER_WG_LOG2;
+  if (!gram_plan(nbonds + 1, nrows, table_bytes, SWAP_B_MAX, SWAP_B_MAX_WIDE, SWAP_B_MIN, 0, nwg, &q)) {
     set_error("internal: bond-swap panel of %zu bytes", q.lds_bytes);
     return 1;
   }
-  q.npanels = (q.nrows + ((int64_t)1 << q.B) - 1) >> q.B;
-  int64_t nwg = (q.nrows + ((int64_t)1 << SWAP_ROWS_PER_WG_LOG2) - 1) >> SWAP_ROWS_PER_WG_LOG2;
-  if (nwg > PM_MAX_WG) nwg = PM_MAX_WG;
-  if (nwg < 1) nwg = 1;
-  q.nwg = (int)nwg;
-  q.per_wg = (q.npanels + nwg - 1) / nwg;
-  q.partial_bytes = (size_t)nwg * (size_t)pm_nacc(q.nb) * 256 * sizeof(double);
   *p = q;
   return 0;
 }
@@ -156,25 +148,8 @@ swap_finalize_kernel(const double *__restrict__ partial, int nwg, int nb, int D,
   pm_tile_finalize(partial, nwg, nb, D, out);
 }
 
-template <int TYPE>
-static int swap_launch_nb(const SwapPlan &p, const c128 *x, const SwapArgs &a, const int64_t *nck, double *partial,
-                          hipStream_t st) {
-  void (*k)(const c128 *, const SwapArgs, const int64_t *, double *) = nullptr;
-  switch (p.nb) {
-    case 1: k = swap_moments_kernel<TYPE, 1>; break;
-    case 2: k = swap_moments_kernel<TYPE, 2>; break;
-    case 3: k = swap_moments_kernel<TYPE, 3>; break;
-    case 4: k = swap_moments_kernel<TYPE, 4>; break;
-    default: set_error("internal: %d tile rows of bond-swap moments", p.nb); return 1;
-  }
-  DNM_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-  hipLaunchKernelGGL(k, dim3((unsigned)p.nwg), dim3(PM_NT), p.lds_bytes, st, x, a, nck, partial);
-  DNM_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_swap_moments(const void *x, int type, int L, int space, int swz, int xsec, int nbonds, const int32_t *bonds,
-                        const SwapPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st) {
+                        const GramPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st) {
   SwapArgs a{};
   a.nrows = p.nrows;
   a.npanels = p.npanels;
@@ -200,12 +175,14 @@ int launch_swap_moments(const void *x, int type, int L, int space, int swz, int 
   }
   const c128 *xp = (const c128 *)x;
   double *pp = (double *)partial;
-  switch (type) {
-    case DNM_FULL: DNM_TRY(swap_launch_nb<DNM_FULL>(p, xp, a, nck, pp, st)); break;
-    case DNM_PARITY: DNM_TRY(swap_launch_nb<DNM_PARITY>(p, xp, a, nck, pp, st)); break;
-    case DNM_SPIN_CONSERVE: DNM_TRY(swap_launch_nb<DNM_SPIN_CONSERVE>(p, xp, a, nck, pp, st)); break;
-    default: set_error("bond-swap moments: subspace type %d", type); return 1;
-  }
+  DNM_TRY(gram_dispatch<false>(type, p.nb, "bond-swap moments", "bond-swap moments: subspace type %d",
+                               [&](auto T, auto NB) {
+    auto k = swap_moments_kernel<decltype(T)::value, decltype(NB)::value>;
+    DNM_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL(k, dim3((unsigned)p.nwg), dim3(PM_NT), p.lds_bytes, st, xp, a, nck, pp);
+    DNM_HIP(hipGetLastError());
+    return 0;
+  }));
   hipLaunchKernelGGL(swap_finalize_kernel, dim3((unsigned)(p.nb * (p.nb + 1) / 2)), dim3(PM_NT), 0, st,
                      (const double *)pp, p.nwg, p.nb, nbonds + 1, (c128 *)out);
   DNM_HIP(hipGetLastError());

@@ -10,12 +10,12 @@
 // is +-1: products are exact, only the accumulation rounds.  The lower-triangle tiles stay in registers for the whole
 // sweep; the four wavefronts of a workgroup are summed in a fixed order through LDS, the workgroups by a second kernel
 // in a fixed order (no atomics: two calls agree to the last bit).  The number of workgroups depends on the number of
-// rows alone, never on the device.
-#include "rdm_tile.h"
+// rows alone, never on the device.  The wave sum and the choice of the kernel instance are gram_tile.h's.
+#include "gram_tile.h"
 
 namespace dnm {
 
-constexpr int ZZ_NT = 256;                // threads of a workgroup: four wavefronts
+constexpr int ZZ_NT = PM_NT;              // threads of a workgroup: four wavefronts
 constexpr int64_t ZZ_MIN_PER_WG = 2048;   // positions a workgroup sweeps at least (8 steps per wavefront)
 constexpr int64_t ZZ_MAX_WG = 1024;       // one resident wavefront per SIMD and workgroup: 4 per SIMD on 256 CUs
 
@@ -128,30 +128,7 @@ zz_moments_kernel(const c128 *__restrict__ x, const SubView sub, int64_t row0, i
     }
   }
 
-  // the four wavefronts, summed in the order ((0 + 1) + 2) + 3; C/D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
-  for (int wv = 1; wv < ZZ_NT / 64; ++wv) {
-    __syncthreads();
-    if (wave == wv) {
-#pragma unroll
-      for (int i = 0; i < NTILE; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) red[i * 256 + (slot + 4 * g) * 16 + r] = acc[i][g];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int i = 0; i < NTILE; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[i][g] += red[i * 256 + (slot + 4 * g) * 16 + r];
-    }
-  }
-  if (wave == 0) {
-    double *out = partial + (int64_t)blockIdx.x * (NTILE * 256);
-#pragma unroll
-    for (int i = 0; i < NTILE; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) out[i * 256 + (slot + 4 * g) * 16 + r] = acc[i][g];
-  }
+  pm_tile_reduce_store<NTILE>(red, wave, slot, r, acc, partial + (int64_t)blockIdx.x * (NTILE * 256));
 }
 
 // M (D x D doubles, row-major) = the workgroups' partial tiles summed in their order; the lower triangle is mirrored
@@ -170,21 +147,6 @@ zz_finalize_kernel(const double *__restrict__ partial, int nwg, int ntiles, int 
   out[b * D + a] = s;
 }
 
-template <int TYPE>
-static int zz_launch_nb(int nb, const c128 *x, const SubView &sub, int64_t row0, int64_t nrows, int64_t per_wg,
-                        int nwg, double *partial, hipStream_t st) {
-  const dim3 grid((unsigned)nwg), block(ZZ_NT);
-  const size_t lds = zz_table_bytes(sub);
-  switch (nb) {
-    case 1: hipLaunchKernelGGL((zz_moments_kernel<TYPE, 1>), grid, block, lds, st, x, sub, row0, nrows, per_wg, partial); break;
-    case 2: hipLaunchKernelGGL((zz_moments_kernel<TYPE, 2>), grid, block, lds, st, x, sub, row0, nrows, per_wg, partial); break;
-    case 3: hipLaunchKernelGGL((zz_moments_kernel<TYPE, 3>), grid, block, lds, st, x, sub, row0, nrows, per_wg, partial); break;
-    case 4: hipLaunchKernelGGL((zz_moments_kernel<TYPE, 4>), grid, block, lds, st, x, sub, row0, nrows, per_wg, partial); break;
-    default: set_error("internal: %d tile rows of sigma-z moments", nb); return 1;
-  }
-  return 0;
-}
-
 int launch_zz_moments(const void *x, const SubView &sub, int64_t row0, int64_t nrows, void *partial, double *out,
                       hipStream_t st) {
   int nb, nwg;
@@ -193,15 +155,11 @@ int launch_zz_moments(const void *x, const SubView &sub, int64_t row0, int64_t n
   zz_plan(sub.L, nrows, &nb, &nwg, &per_wg, &bytes);
   const c128 *xp = (const c128 *)x;
   double *pp = (double *)partial;
-  switch (sub.type) {
-    case DNM_FULL: DNM_TRY(zz_launch_nb<DNM_FULL>(nb, xp, sub, row0, nrows, per_wg, nwg, pp, st)); break;
-    case DNM_PARITY: DNM_TRY(zz_launch_nb<DNM_PARITY>(nb, xp, sub, row0, nrows, per_wg, nwg, pp, st)); break;
-    case DNM_SPIN_CONSERVE:
-      DNM_TRY(zz_launch_nb<DNM_SPIN_CONSERVE>(nb, xp, sub, row0, nrows, per_wg, nwg, pp, st));
-      break;
-    case DNM_EXPLICIT: DNM_TRY(zz_launch_nb<DNM_EXPLICIT>(nb, xp, sub, row0, nrows, per_wg, nwg, pp, st)); break;
-    default: set_error("bad subspace type"); return 1;
-  }
+  DNM_TRY(gram_dispatch<true>(sub.type, nb, "sigma-z moments", "bad subspace type", [&](auto T, auto NB) {
+    hipLaunchKernelGGL((zz_moments_kernel<decltype(T)::value, decltype(NB)::value>), dim3((unsigned)nwg), dim3(ZZ_NT),
+                       zz_table_bytes(sub), st, xp, sub, row0, nrows, per_wg, pp);
+    return 0;
+  }));
   const int ntiles = nb * (nb + 1) / 2;
   hipLaunchKernelGGL(zz_finalize_kernel, dim3((unsigned)ntiles), dim3(ZZ_NT), 0, st, (const double *)pp, nwg, ntiles,
                      sub.L + 1, out);

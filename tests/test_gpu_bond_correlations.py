@@ -1,6 +1,6 @@
 """
-All bond-swap (dimer-dimer) correlators of a state in one matrix-core pass (csrc/swap_kernels.hip, dnm_swap_moments,
-backend.swap_moments, computations.bond_correlations).
+All bond-swap (dimer-dimer) correlators of a state in one matrix-core pass (csrc/swap_kernels.hip, csrc/gram_tile.h,
+csrc/observables.cpp: dnm_swap_moments; backend.swap_moments, computations.bond_correlations).
 
 The reference is numpy on the host: the configurations of the subspace, the operand matrix A[:, 0] = psi, A[:, 1 + m] =
 psi gathered through state_to_idx of the configurations with bits a_m and b_m exchanged, and G = A^H A.  For a state on

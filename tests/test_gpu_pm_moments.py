@@ -1,6 +1,6 @@
 """
-All <sigma+_i sigma-_j> of a state in one matrix-core pass (csrc/pm_kernels.hip, dnm_pm_moments, backend.pm_moments,
-computations.sigma_pm_correlations / spin_correlations).
+All <sigma+_i sigma-_j> of a state in one matrix-core pass (csrc/pm_kernels.hip, csrc/gram_tile.h,
+csrc/observables.cpp: dnm_pm_moments; backend.pm_moments, computations.sigma_pm_correlations / spin_correlations).
 
 The reference is numpy on the host: the configurations of the subspace and of the row sector (sigma_minus(j) sets bit
 j: every configuration for Full, the opposite parity for Parity, k + 1 set bits for SpinConserve(L, k)), the operand
@@ -144,6 +144,7 @@ EXACT = [
     pytest.param(lambda: Parity('odd', L=17), 1 << 16, id="parity17_odd"),
     pytest.param(lambda: SpinConserve(16, 8), 12870, id="sc16_8"),
     pytest.param(lambda: SpinConserve(34, 2), 561, id="sc34_2"),
+    pytest.param(lambda: SpinConserve(50, 2), 1225, id="sc50_2"),       # four tile rows, 19 600 rows
     pytest.param(lambda: SpinConserve(12, 12), 1, id="sc12_12"),
     pytest.param(lambda: SpinConserve(12, 0), 1, id="sc12_0"),
 ]

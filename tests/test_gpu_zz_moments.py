@@ -1,6 +1,6 @@
 """
-All <sigmaz_i> and <sigmaz_i sigmaz_j> of a state in one matrix-core pass (csrc/zz_kernels.hip, dnm_zz_moments,
-backend.zz_moments, computations.sigmaz_correlations).
+All <sigmaz_i> and <sigmaz_i sigmaz_j> of a state in one matrix-core pass (csrc/zz_kernels.hip, csrc/gram_tile.h,
+csrc/observables.cpp: dnm_zz_moments; backend.zz_moments, computations.sigmaz_correlations).
 
 The reference is numpy on the host: the configurations of the subspace, a sign matrix S~ = (1, s_0, ..., s_{L-1}) from
 their bits and S~^T (w S~) with w = |psi|^2.  States with small integer amplitudes make every weight an integer <= 18

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Times the one-pass bond-swap moments (csrc/swap_kernels.hip, backend.swap_moments) against the loop they replace.
+"""Times the one-pass bond-swap moments (csrc/swap_kernels.hip, csrc/gram_tile.h, csrc/observables.cpp,
+backend.swap_moments) against the loop they replace.
 
 bond_correlations_timing.py [STEP ...]    steps: kagome30 kagome30x full26 full30 (default: all four)
 

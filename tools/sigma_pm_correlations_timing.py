@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Times the one-pass sigma+ sigma- moments (csrc/pm_kernels.hip, backend.pm_moments) against the route they replace.
+"""Times the one-pass sigma+ sigma- moments (csrc/pm_kernels.hip, csrc/gram_tile.h, csrc/observables.cpp,
+backend.pm_moments) against the route they replace.
 
 sigma_pm_correlations_timing.py [STEP ...]    steps: full26 full30 sc32 sc30 sc28 (default: full26 full30 sc32)
 

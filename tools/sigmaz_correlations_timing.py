@@ -1,7 +1,9 @@
 #!/usr/bin/env python
-"""Times the one-pass sigma-z moments (csrc/zz_kernels.hip, backend.zz_moments) against the route they replace.
+"""Times the one-pass sigma-z moments (csrc/zz_kernels.hip, csrc/gram_tile.h, backend.zz_moments) against the route
+they replace.
 
-sigmaz_correlations_timing.py [STEP ...]    steps: full26 full30 sc32 (default: all three)
+sigmaz_correlations_timing.py [STEP ...]    steps: full26 full30 sc32 sc30 (default: the first three; sc30 is the
+                                            two-tile-row SpinConserve instance, L = 16 ... 31)
 
 Every step runs in a process of its own under its own time limit; the first failure ends the run.  The output is
 appended to profiles/sigmaz_correlations.txt as well.  Per shape, on a random state:
@@ -23,7 +25,7 @@ import time
 os.environ.setdefault("DNM_EXPERIMENTAL", "1")   # tools drive experiment knobs
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LIMITS = {"full26": 240, "full30": 420, "sc32": 480}
+LIMITS = {"full26": 240, "full30": 420, "sc32": 480, "sc30": 480}
 REPS = 11
 HBM_BYTES_S = 8.0e12        # MI355X: HBM3E peak
 MFMA_FLOP_S = 78.6e12       # MI355X: fp64 matrix peak
@@ -102,7 +104,8 @@ def _plain(sub_c):
 
 def step(name):
     from dynamite_amd.subspaces import Full, SpinConserve
-    run({"full26": lambda: Full(L=26), "full30": lambda: Full(L=30), "sc32": lambda: SpinConserve(32, 16)}[name]())
+    run({"full26": lambda: Full(L=26), "full30": lambda: Full(L=30), "sc32": lambda: SpinConserve(32, 16),
+         "sc30": lambda: SpinConserve(30, 15)}[name]())
 
 
 def main():
