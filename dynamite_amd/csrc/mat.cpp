@@ -1,9 +1,7 @@
-// C ABI: device helpers, subspace maps, and the shell matrix (create / mult /
-// norm / diagonal / destroy); the observables of a state are in observables.cpp.
+// C ABI: device helpers, subspace maps, and the shell matrix (create / norm / diagonal / exports / destroy); its
+// multiplies are in mat_mult.cpp, the observables of a state in observables.cpp.
 // See include/dynamite_amd.h for the reference interfaces each entry point replaces.
 #include "passes.h"
-#include "vec_api.h"
-#include "row_fused.h"
 
 #include <algorithm>
 #include <cstring>
@@ -160,31 +158,6 @@ int PassRecords::upload() {
 
 static hipStream_t S(void *stream) { return (hipStream_t)stream; }
 
-// What one call adds to the description of a pass
-struct PassCall {
-  const void *zinit = nullptr, *zinit2 = nullptr;     // DevPass::zinit ... block_offset
-  double zscale = 0.0, z2re = 0.0, z2im = 0.0;
-  double *dot_out = nullptr;
-  uint32_t block_offset = 0;
-  unsigned nparts = 1;             // > 1: the 1 / nparts of the pass's workgroups that starts at block_offset
-};
-
-static int launch_pass(const dnm_mat *A, const PassOnDevice &p, const PassCall &c, const void *x, void *y,
-                       const void *xr, hipStream_t st) {
-  DevPass d = p.runs().desc;
-  d.zinit = c.zinit; d.zscale = c.zscale;
-  d.zinit2 = c.zinit2; d.z2re = c.z2re; d.z2im = c.z2im;
-  d.dot_out = c.dot_out;
-  d.block_offset = c.block_offset;
-  return launch_tile_pass(d, d.tile_bits, d.log_rows, (A->flags & DNM_MAT_USE_GLDS) != 0, p.n_eff, x, y, xr, st, c.nparts,
-                          p.reduced ? &p.reduced->flip : nullptr);
-}
-
-// partial sums a pass writes to dot_out: one per tile
-static size_t pass_dot_partials(const dnm_mat *, const PassOnDevice &p) {
-  return (size_t)1 << (p.n_eff - p.whole.desc.tile_bits);
-}
-
 // the exports: pass lookup, and the checked copy-out of a host vector (item: the caller's size of one element; an empty
 // vector copies nothing and, unless `strict`, checks nothing)
 static int export_lookup(const dnm_mat *A, int remote, int idx, const PassOnDevice **p) {
@@ -309,6 +282,20 @@ int dnm_check_conserves(int64_t nmasks, const int64_t *masks, const int64_t *mas
 }
 
 // ---- shell matrix -------------------------------------------------------------
+// The patterns of `bits` <= 16 bits grouped by popcount, ascending inside a group (colex order = numeric order): group j
+// starts at table[off[j]]
+static void popcount_groups(int bits, std::vector<uint16_t> *table, int32_t off[18]) {
+  const int n = 1 << bits;
+  table->resize((size_t)n);
+  int cnt[18] = {0};
+  for (int v = 0; v < n; ++v) ++cnt[__builtin_popcount(v) + 1];
+  for (int j = 0; j < 17; ++j) { cnt[j + 1] += cnt[j]; off[j] = cnt[j]; }
+  off[17] = n;
+  int fill[17];
+  for (int j = 0; j < 17; ++j) fill[j] = off[j];
+  for (int v = 0; v < n; ++v) (*table)[fill[__builtin_popcount(v)]++] = (uint16_t)v;
+}
+
 // Decide whether the SpinConserve block kernel runs and build its table.  DNM_SC_BLOCK = 0 (row kernel),
 // 10 / 13 (low bits per block); default: 13 when the blocks are large enough to fill a workgroup.
 static int setup_sc_block(dnm_mat *A) {
@@ -326,14 +313,8 @@ static int setup_sc_block(dnm_mat *A) {
   if (L <= lb || L - lb > 48) return 0;
   if (!forced && (A->M >> (L - lb)) < 256) return 0;     // blocks too small on average: one row per thread instead
   if (!forced && 2 * A->sc_nfast < (int)A->masks.size()) return 0;   // mostly non-chain masks: they take the per-row path anyway
-  std::vector<uint16_t> tab((size_t)1 << lb);
-  int cnt[18] = {0};
-  for (int v = 0; v < (1 << lb); ++v) ++cnt[__builtin_popcount(v) + 1];
-  for (int j = 0; j < 17; ++j) { cnt[j + 1] += cnt[j]; A->scblock.off[j] = cnt[j]; }
-  A->scblock.off[17] = 1 << lb;
-  int fill[17];
-  for (int j = 0; j < 17; ++j) fill[j] = A->scblock.off[j];
-  for (int v = 0; v < (1 << lb); ++v) tab[fill[__builtin_popcount(v)]++] = (uint16_t)v;
+  std::vector<uint16_t> tab;
+  popcount_groups(lb, &tab, A->scblock.off);
   DNM_TRY(A->d_scblock.upload(tab.data(), tab.size() * sizeof(uint16_t)));
   A->scblock.lowtab = (const uint16_t *)A->d_scblock.p;
   int64_t hf = sub_i2s(A->row0, h) >> lb, hl = sub_i2s(A->row0 + A->m_local - 1, h) >> lb;
@@ -403,6 +384,216 @@ static int build_passes(const dnm_mat &A, const std::vector<PassSpec> &specs, st
   for (const PassSpec &ps : specs) {
     out->emplace_back(new PassOnDevice());
     DNM_TRY(build_pass(A, ps, out->back().get()));
+  }
+  return 0;
+}
+
+// dnm_mat_create, step 1: the device tables of the row kernels.  The generic ones always (norm and diagonal use them);
+// for two SpinConserve subspaces the per-mask table `scm`, the 16-bit unranking table and, in reference order, the
+// block kernel's.  A host-only handle has none of them.
+static int setup_row_tables(dnm_mat *A, const std::vector<ScMask> &scm) {
+  if (A->host_only) return 0;
+  DNM_TRY(A->d_masks.upload(A->masks.data(), A->masks.size() * 8));
+  DNM_TRY(A->d_offsets.upload(A->mask_offsets.data(), A->mask_offsets.size() * 8));
+  DNM_TRY(A->d_signs.upload(A->signs.data(), A->signs.size() * 8));
+  DNM_TRY(A->d_rcoeffs.upload(A->real_coeffs.data(), A->real_coeffs.size() * 8));
+  A->dmsc.nmasks = (int32_t)A->masks.size();
+  A->dmsc.masks = (const int64_t *)A->d_masks.p;
+  A->dmsc.mask_offsets = (const int64_t *)A->d_offsets.p;
+  A->dmsc.signs = (const int64_t *)A->d_signs.p;
+  A->dmsc.real_coeffs = (const double *)A->d_rcoeffs.p;
+  if (A->left.host.type == DNM_SPIN_CONSERVE && A->right.host.type == DNM_SPIN_CONSERVE) {
+    A->sc_nfast = 0;
+    for (const ScMask &e : scm) A->sc_nfast += e.fast ? 1 : 0;
+    DNM_TRY(A->d_scmasks.upload(scm.data(), scm.size() * sizeof(ScMask)));
+    std::vector<uint16_t> low;
+    popcount_groups(16, &low, A->sclow.off);
+    DNM_TRY(A->d_sclow.upload(low.data(), low.size() * sizeof(uint16_t)));
+    A->sclow.tab = (const uint16_t *)A->d_sclow.p;
+    if (!A->use_sc3) DNM_TRY(setup_sc_block(A));
+  }
+  return 0;
+}
+
+// the operator arrays of a handle (dnm_mat::masks ... real_coeffs) in another labelling of the sites
+namespace {
+struct OpArrays {
+  std::vector<int64_t> masks, offsets, signs;
+  std::vector<double> coeffs;
+};
+}  // namespace
+
+// The operator as the kernels of a relabelled layout see it: masks and signs bit by bit into the layout's labelling, the
+// mask groups sorted again (terms keep their order inside a group; a coefficient is unchanged: it multiplies the same
+// product of Pauli matrices).  No relabelling: the arrays as they are.
+static OpArrays relabelled_operator(const dnm_mat &A, const Sc3Perm &P) {
+  OpArrays o{A.masks, A.mask_offsets, A.signs, A.real_coeffs};
+  if (!P.on) return o;
+  const int L = A.left.host.L;
+  const int64_t nmasks = (int64_t)A.masks.size();
+  std::vector<int64_t> order((size_t)nmasks);
+  std::vector<uint64_t> nm((size_t)nmasks);
+  for (int64_t i = 0; i < nmasks; ++i) {
+    order[(size_t)i] = i;
+    nm[(size_t)i] = sc3_permute((uint64_t)A.masks[(size_t)i], P.to_int, L);
+  }
+  std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return nm[(size_t)x] < nm[(size_t)y]; });
+  o.masks.clear(); o.signs.clear(); o.coeffs.clear();
+  o.offsets.assign(1, 0);
+  for (int64_t q = 0; q < nmasks; ++q) {
+    const int64_t i = order[(size_t)q];
+    o.masks.push_back((int64_t)nm[(size_t)i]);
+    for (int64_t t = A.mask_offsets[(size_t)i]; t < A.mask_offsets[(size_t)i + 1]; ++t) {
+      o.signs.push_back((int64_t)sc3_permute((uint64_t)A.signs[(size_t)t], P.to_int, L));
+      o.coeffs.push_back(A.real_coeffs[(size_t)t]);
+    }
+    o.offsets.push_back((int64_t)o.signs.size());
+  }
+  return o;
+}
+
+// dnm_mat_create, step 2: a SpinConserve pair whose vectors are in the internal layout (sc3.h) -- the layout, the
+// rank's share of it, the operator in the layout's site labelling (left / right: the caller's descriptors, for their
+// site_perm) and the tables of its kernels (sc3_tables.cpp); m_local / n_local / rows_local / row0 then describe the share.
+// scm: the per-mask table in reference labelling.
+static int setup_sc3(dnm_mat *A, const dnm_subspace *left, const dnm_subspace *right, std::vector<ScMask> scm) {
+  const SubView &h = A->left.host;
+  const Sc3Layout *ly = sc3_get(h.L, h.k, sc3_code_a(h.sc3), sc3_code_w(h.sc3), !A->host_only, sc3_code_order(h.sc3));
+  DNM_CHECK(ly, "could not build the SpinConserve vector layout");
+  A->sc3.reset(new Sc3Mat());
+  // partitioned: whole T blocks per rank (a contiguous range of both the internal layout and the reference order)
+  std::vector<uint32_t> Tb = sc3_partition(*ly, A->nranks);
+  if (A->xparity) {
+    // the half whose top bit is clear, as a PLACE in the block sequence (a layout with empty blocks -- k > a + w or
+    // t > k -- has fewer than 2^(t-1) blocks below it); only block order 0 keeps that half together
+    DNM_CHECK(ly->order == 0, "XParity on a SpinConserve layout in block order %d: the half whose top bit is clear is "
+              "no range of that layout", ly->order);
+    Tb = {0u, sc3_top_clear_blocks(*ly)};
+  }
+  const bool want_real = (A->flags & DNM_MAT_REAL_PACKED) != 0;
+  // site relabelling of the vectors (dnm_subspace.site_perm): the kernels of the layout see the operator in it
+  Sc3Perm P, Pr;
+  DNM_CHECK(sc3_perm_make(left->site_perm, h.L, &P) && sc3_perm_make(right->site_perm, h.L, &Pr),
+            "site_perm is not a permutation of the %d spins", h.L);
+  DNM_CHECK(memcmp(P.to_int, Pr.to_int, sizeof P.to_int) == 0, "left and right vectors must share their site relabelling");
+  DNM_CHECK(!P.on || A->nranks == 1, "a relabelled SpinConserve layout is not partitioned over ranks");
+  DNM_CHECK(!A->xparity || P.to_int[h.L - 1] == h.L - 1, "XParity: the site relabelling must keep spin L-1 in place");
+  A->sc3->perm = P;
+  const OpArrays o = relabelled_operator(*A, P);
+  if (P.on) scm = sc_masks(o.masks, o.offsets, o.signs, o.coeffs, h.L, A->xparity);
+  A->dmsc_sc3 = A->dmsc;
+  if (P.on && !A->host_only) {           // the row kernel's tables in the layout's labelling
+    DNM_TRY(A->d_pmasks.upload(o.masks.data(), o.masks.size() * 8));
+    DNM_TRY(A->d_poffsets.upload(o.offsets.data(), o.offsets.size() * 8));
+    DNM_TRY(A->d_psigns.upload(o.signs.data(), o.signs.size() * 8));
+    DNM_TRY(A->d_prcoeffs.upload(o.coeffs.data(), o.coeffs.size() * 8));
+    A->dmsc_sc3.masks = (const int64_t *)A->d_pmasks.p;
+    A->dmsc_sc3.mask_offsets = (const int64_t *)A->d_poffsets.p;
+    A->dmsc_sc3.signs = (const int64_t *)A->d_psigns.p;
+    A->dmsc_sc3.real_coeffs = (const double *)A->d_prcoeffs.p;
+  }
+  DNM_TRY(A->sc3->init(ly, o.masks, o.offsets, o.signs, o.coeffs, scm, !A->host_only, Tb[A->rank], Tb[A->rank + 1],
+                       want_real));
+  if (const char *e = knob("DNM_SC3_TILED")) if (e[0] == '0') A->sc3->tiled = false;     // tests: the row kernel
+  if (const char *e = knob("DNM_SC3_DIAG")) if (e[0] == 'c' && A->sc3->diag_mode == 2) A->sc3->diag_mode = 1;
+  // (timing probe, WRONG results: the passes without any diagonal -- what dropping the cached diagonal's 8 B/row could save)
+  if (const char *e = knob("DNM_SC3_DIAG")) if (e[0] == 'n') A->sc3->diag_mode = 0;
+  int64_t is, il, ns, nl;
+  sc3_range(*ly, Tb[A->rank], Tb[A->rank + 1], &is, &il, &ns, &nl);
+  A->m_local = A->n_local = il;          // what the vector kernels sweep: rows + padding
+  A->rows_local = nl;
+  // first row in reference order (norm / diagonal kernels).  Block order 0: the share is the reference rows
+  // [row0, row0 + rows_local).  Any other order: rows_local still counts the share's rows, but they are no range of
+  // the reference order and row0 is -1 on every share that does not start the sequence -- whatever walks reference
+  // rows asks ref_side first or walks sc3_ref_runs (dnm_mat_norm_inf)
+  A->row0 = ns;
+  if (want_real) {
+    // real vectors in the same positions of the layout, one double each: a vector is il / 2 complex128 elements for
+    // everything that sweeps it (the Krylov kernels); the two tiled passes only (chain operators, real symmetric)
+    // Partitions: every position the C ABI speaks of for such a handle -- ownership, column windows, chunk maps,
+    // window starts -- counts complex128 ELEMENTS (pairs of entries; blocks of equal top bits start at multiples of 8
+    // entries), so the caller's exchange code is the one it runs for complex vectors, on half the bytes
+    DNM_CHECK(A->sc3->tiled && A->sc3->sym,
+              "operator has an imaginary matrix element or is not a sum of pair hops: no real-packed form in this layout");
+    A->real_packed = true;
+    A->m_local = A->n_local = il / 2;
+  }
+  return 0;
+}
+
+// dnm_mat_create, step 3: a Full / Parity pair -- the operator in index-space form, the plan with the defaults of its
+// configuration and, when the plan is tiled, the passes' records (passes.cpp) and their upload
+static int setup_hypercube(dnm_mat *A) {
+  const int flags = A->flags;
+  DNM_TRY(build_opform(*A, &A->op));
+  if (flags & DNM_MAT_REAL_PACKED) {
+    // (partitions: the rank bits are the top index bits, the packed bit is bit 0 -- the partner exchange of the packed
+    // operator is that of an operator on one bit less; the transposed exchange is not built for it)
+    // (XParity on top: the reduced operator is packed like any other -- its flip-composed masks reach index bit 0, the
+    // lane, like every odd mask -- and loses its top index bit below)
+    DNM_CHECK(A->M == A->N, "real-packed operators: square");
+    DNM_TRY(pack_opform(&A->op));
+    A->real_packed = true;
+    A->M /= 2; A->N /= 2; A->m_local /= 2; A->n_local /= 2;         // complex128 elements, two amplitudes each
+  }
+  if (A->xparity) {
+    // rows and columns have the top index bit clear: the hypercube loses one dimension
+    const uint64_t topbit = (uint64_t)1 << (A->op.n - 1);
+    for (RowMask &rm : A->op.masks) {
+      DNM_CHECK(!(rm.mask & topbit), "internal: XParity mask reaches the top index bit");
+      for (RowTerm &t : rm.terms) t.sign &= ~topbit;
+    }
+    A->op.n -= 1;
+  }
+  PlanConfig cfg = plan_config_from_env();
+  if (const int fa = (flags >> DNM_MAT_AMIN_SHIFT) & 0xff) cfg.amin = fa;      // caller-chosen run length of window tiles
+  DNM_CHECK(A->left.host.swz == A->right.host.swz, "left and right vectors of a Full/Parity pair must share a layout");
+  cfg.swz = A->left.host.swz;
+  int nl = A->op.n;            // index bits of a rank's block: what the measured defaults below go by
+  for (int r = A->nranks; r > 1; r >>= 1) --nl;
+  if (cfg.logR < 0) {
+    // measured: in index order 16 rows per thread pay from 2^26 local amplitudes on (profiles/r01_sweep6.txt);
+    // with swizzled vectors 8 rows beat 16 at every size (profiles/r02_exp3_v2.txt), and once the window pass
+    // runs first and the accumulating pass carries the diagonal, 4 rows per thread (two 1024-thread workgroups,
+    // 32 waves per CU) beat 8: L=30 16.9 -> 16.5 ms, 2-3 % from 2^26 amplitudes on
+    // (profiles/r02_exp46_rows4_series.txt, r02_exp47_rows4_sizes.txt)
+    cfg.logR = cfg.swz ? 2 : (nl >= 26 ? 4 : 3);
+  }
+  if (cfg.diag_last < 0) cfg.diag_last = cfg.swz ? 1 : 0;
+  if (cfg.window_first < 0) {
+    // which pass writes y and which adds to it: the window pass is bound by its bytes (48 B/amp when it
+    // accumulates, at the streaming rate), the contiguous pass by its records (8.0 ms for 32.9 B/amp) -- so the y
+    // read belongs to the latter.  With swizzled vectors (in index order the window pass's gathers do not merge
+    // and it is the slow one either way, profiles/r01_prof_multi18.txt): L=30 17.5 -> 17.0 ms, L=28 4.43 -> 4.22,
+    // L=26 1.09 -> 1.07; level or worse while both vectors fit in the Infinity Cache
+    // (profiles/r02_exp41_pass_order.txt, r02_exp42_window_first_wide.txt)
+    cfg.window_first = (cfg.swz && nl >= 25) ? 1 : 0;
+  }
+  if (!tile_config_supported(cfg.B, cfg.logR)) {
+    set_error("unsupported tile configuration B=%d logR=%d", cfg.B, cfg.logR);
+    return 1;
+  }
+  DNM_TRY(make_plan(A->op, A->rank, A->nranks, cfg, &A->plan));
+  if (flags & DNM_MAT_FORCE_GATHER) A->plan.use_tiled = false;
+  DNM_CHECK(!A->real_packed || A->plan.use_tiled, "real-packed operators run on the tiled kernel only (vector too small)");
+  if (A->nranks > 1 && !A->plan.use_tiled) {
+    // blocks smaller than one tile (or DNM_MAT_FORCE_GATHER): the window partition of the row kernel
+    A->plan.remote.clear();
+    A->plan.sends.clear();
+  }
+  if (A->plan.use_tiled) {
+    DNM_TRY(build_passes(*A, A->plan.local, &A->local_passes));
+    DNM_TRY(build_passes(*A, A->plan.remote, &A->remote_passes));
+    // flip-flop records (plan.h: DevFlip): decided for the operator as a whole, from its passes as they stand
+    decide_flip_bonds(A);
+    for (size_t i = 0; i < A->plan.local.size(); ++i)
+      DNM_TRY(build_flip_pass(*A, A->plan.local[i], A->local_passes[i].get()));
+    // the diagonal of what the kernel runs on as tables (DevPass::dblock), where it qualifies
+    for (auto *v : {&A->local_passes, &A->remote_passes})
+      for (auto &p : *v) DNM_TRY(build_diag_tables(*A, p.get()));
+    if (!A->host_only)
+      for (auto *v : {&A->local_passes, &A->remote_passes})
+        for (auto &p : *v) DNM_TRY(p->runs().upload());
   }
   return 0;
 }
@@ -492,200 +683,17 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
   std::vector<ScMask> scm;
   if (lt == DNM_SPIN_CONSERVE && rt == DNM_SPIN_CONSERVE)
     scm = sc_masks(A->masks, A->mask_offsets, A->signs, A->real_coeffs, A->left.host.L, A->xparity);
-  // tables for the generic kernels (always: norm and diagonal use them)
-  if (!A->host_only) {
-  DNM_TRY(A->d_masks.upload(A->masks.data(), A->masks.size() * 8));
-  DNM_TRY(A->d_offsets.upload(A->mask_offsets.data(), A->mask_offsets.size() * 8));
-  DNM_TRY(A->d_signs.upload(A->signs.data(), A->signs.size() * 8));
-  DNM_TRY(A->d_rcoeffs.upload(A->real_coeffs.data(), A->real_coeffs.size() * 8));
-  A->dmsc.nmasks = (int32_t)nmasks;
-  A->dmsc.masks = (const int64_t *)A->d_masks.p;
-  A->dmsc.mask_offsets = (const int64_t *)A->d_offsets.p;
-  A->dmsc.signs = (const int64_t *)A->d_signs.p;
-  A->dmsc.real_coeffs = (const double *)A->d_rcoeffs.p;
-  if (lt == DNM_SPIN_CONSERVE && rt == DNM_SPIN_CONSERVE) {
-    A->sc_nfast = 0;
-    for (const ScMask &e : scm) A->sc_nfast += e.fast ? 1 : 0;
-    DNM_TRY(A->d_scmasks.upload(scm.data(), scm.size() * sizeof(ScMask)));
-    // 16-bit patterns grouped by popcount, ascending inside a group (colex order = numeric order)
-    std::vector<uint16_t> low(65536);
-    int cnt[18] = {0};
-    for (int v = 0; v < 65536; ++v) ++cnt[__builtin_popcount(v) + 1];
-    for (int j = 0; j < 17; ++j) { cnt[j + 1] += cnt[j]; A->sclow.off[j] = cnt[j]; }
-    A->sclow.off[17] = 65536;
-    int fill[17];
-    for (int j = 0; j < 17; ++j) fill[j] = A->sclow.off[j];
-    for (int v = 0; v < 65536; ++v) low[fill[__builtin_popcount(v)]++] = (uint16_t)v;
-    DNM_TRY(A->d_sclow.upload(low.data(), low.size() * sizeof(uint16_t)));
-    A->sclow.tab = (const uint16_t *)A->d_sclow.p;
-    if (!A->use_sc3) DNM_TRY(setup_sc_block(A.get()));
-  }
-  }
-  if (A->use_sc3) {
-    const SubView &h = A->left.host;
-    const Sc3Layout *ly = sc3_get(h.L, h.k, sc3_code_a(h.sc3), sc3_code_w(h.sc3), !A->host_only, sc3_code_order(h.sc3));
-    DNM_CHECK(ly, "could not build the SpinConserve vector layout");
-    A->sc3.reset(new Sc3Mat());
-    // partitioned: whole T blocks per rank (a contiguous range of both the internal layout and the reference order)
-    std::vector<uint32_t> Tb = sc3_partition(*ly, A->nranks);
-    if (A->xparity) {
-      // the half whose top bit is clear, as a PLACE in the block sequence (a layout with empty blocks -- k > a + w or
-      // t > k -- has fewer than 2^(t-1) blocks below it); only block order 0 keeps that half together
-      DNM_CHECK(ly->order == 0, "XParity on a SpinConserve layout in block order %d: the half whose top bit is clear is "
-                "no range of that layout", ly->order);
-      Tb = {0u, sc3_top_clear_blocks(*ly)};
-    }
-    const bool want_real = (flags & DNM_MAT_REAL_PACKED) != 0;
-    // site relabelling of the vectors (dnm_subspace.site_perm): the kernels of the layout see the operator in it
-    Sc3Perm P, Pr;
-    DNM_CHECK(sc3_perm_make(left->site_perm, h.L, &P) && sc3_perm_make(right->site_perm, h.L, &Pr),
-              "site_perm is not a permutation of the %d spins", h.L);
-    DNM_CHECK(memcmp(P.to_int, Pr.to_int, sizeof P.to_int) == 0, "left and right vectors must share their site relabelling");
-    DNM_CHECK(!P.on || A->nranks == 1, "a relabelled SpinConserve layout is not partitioned over ranks");
-    DNM_CHECK(!A->xparity || P.to_int[h.L - 1] == h.L - 1, "XParity: the site relabelling must keep spin L-1 in place");
-    A->sc3->perm = P;
-    std::vector<int64_t> pmasks = A->masks, poffs = A->mask_offsets, psigns = A->signs;
-    std::vector<double> pcoef = A->real_coeffs;
-    if (P.on) {
-      // masks and signs bit by bit into the layout's labelling; the mask groups sorted again (terms keep their order
-      // inside a group; a coefficient is unchanged: it multiplies the same product of Pauli matrices)
-      std::vector<int64_t> order((size_t)nmasks);
-      std::vector<uint64_t> nm((size_t)nmasks);
-      for (int64_t i = 0; i < nmasks; ++i) {
-        order[(size_t)i] = i;
-        nm[(size_t)i] = sc3_permute((uint64_t)A->masks[(size_t)i], P.to_int, h.L);
-      }
-      std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return nm[(size_t)x] < nm[(size_t)y]; });
-      pmasks.clear(); psigns.clear(); pcoef.clear();
-      poffs.assign(1, 0);
-      for (int64_t q = 0; q < nmasks; ++q) {
-        const int64_t i = order[(size_t)q];
-        pmasks.push_back((int64_t)nm[(size_t)i]);
-        for (int64_t t = A->mask_offsets[(size_t)i]; t < A->mask_offsets[(size_t)i + 1]; ++t) {
-          psigns.push_back((int64_t)sc3_permute((uint64_t)A->signs[(size_t)t], P.to_int, h.L));
-          pcoef.push_back(A->real_coeffs[(size_t)t]);
-        }
-        poffs.push_back((int64_t)psigns.size());
-      }
-      scm = sc_masks(pmasks, poffs, psigns, pcoef, h.L, A->xparity);
-      if (!A->host_only) {           // the row kernel's tables in the layout's labelling
-        DNM_TRY(A->d_pmasks.upload(pmasks.data(), pmasks.size() * 8));
-        DNM_TRY(A->d_poffsets.upload(poffs.data(), poffs.size() * 8));
-        DNM_TRY(A->d_psigns.upload(psigns.data(), psigns.size() * 8));
-        DNM_TRY(A->d_prcoeffs.upload(pcoef.data(), pcoef.size() * 8));
-      }
-    }
-    A->dmsc_sc3 = A->dmsc;
-    if (P.on && !A->host_only) {
-      A->dmsc_sc3.masks = (const int64_t *)A->d_pmasks.p;
-      A->dmsc_sc3.mask_offsets = (const int64_t *)A->d_poffsets.p;
-      A->dmsc_sc3.signs = (const int64_t *)A->d_psigns.p;
-      A->dmsc_sc3.real_coeffs = (const double *)A->d_prcoeffs.p;
-    }
-    DNM_TRY(A->sc3->init(ly, pmasks, poffs, psigns, pcoef, scm, !A->host_only, Tb[A->rank],
-                         Tb[A->rank + 1], want_real));
-    if (const char *e = knob("DNM_SC3_TILED")) if (e[0] == '0') A->sc3->tiled = false;     // tests: the row kernel
-    if (const char *e = knob("DNM_SC3_DIAG")) if (e[0] == 'c' && A->sc3->diag_mode == 2) A->sc3->diag_mode = 1;
-    // (timing probe, WRONG results: the passes without any diagonal -- what dropping the cached diagonal's 8 B/row could save)
-    if (const char *e = knob("DNM_SC3_DIAG")) if (e[0] == 'n') A->sc3->diag_mode = 0;
-    int64_t is, il, ns, nl;
-    sc3_range(*ly, Tb[A->rank], Tb[A->rank + 1], &is, &il, &ns, &nl);
-    A->m_local = A->n_local = il;          // what the vector kernels sweep: rows + padding
-    A->rows_local = nl;
-    // first row in reference order (norm / diagonal kernels).  Block order 0: the share is the reference rows
-    // [row0, row0 + rows_local).  Any other order: rows_local still counts the share's rows, but they are no range of
-    // the reference order and row0 is -1 on every share that does not start the sequence -- whatever walks reference
-    // rows asks ref_side first or walks sc3_ref_runs (dnm_mat_norm_inf)
-    A->row0 = ns;
-    if (want_real) {
-      // real vectors in the same positions of the layout, one double each: a vector is il / 2 complex128 elements for
-      // everything that sweeps it (the Krylov kernels); the two tiled passes only (chain operators, real symmetric)
-      // Partitions: every position the C ABI speaks of for such a handle -- ownership, column windows, chunk maps,
-      // window starts -- counts complex128 ELEMENTS (pairs of entries; blocks of equal top bits start at multiples of 8
-      // entries), so the caller's exchange code is the one it runs for complex vectors, on half the bytes
-      DNM_CHECK(A->sc3->tiled && A->sc3->sym,
-                "operator has an imaginary matrix element or is not a sum of pair hops: no real-packed form in this layout");
-      A->real_packed = true;
-      A->m_local = A->n_local = il / 2;
-    }
-  } else if (flags & DNM_MAT_REAL_PACKED) {
-    DNM_CHECK(A->hypercube, "real-packed operators: Full / Parity pairs, or a SpinConserve pair in the internal layout");
-  }
-
-  if (A->hypercube) {
-    DNM_TRY(build_opform(*A, &A->op));
-    if (flags & DNM_MAT_REAL_PACKED) {
-      // (partitions: the rank bits are the top index bits, the packed bit is bit 0 -- the partner exchange of the packed
-      // operator is that of an operator on one bit less; the transposed exchange is not built for it)
-      // (XParity on top: the reduced operator is packed like any other -- its flip-composed masks reach index bit 0, the
-      // lane, like every odd mask -- and loses its top index bit below)
-      DNM_CHECK(A->M == A->N, "real-packed operators: square");
-      DNM_TRY(pack_opform(&A->op));
-      A->real_packed = true;
-      A->M /= 2; A->N /= 2; A->m_local /= 2; A->n_local /= 2;         // complex128 elements, two amplitudes each
-    }
-    if (A->xparity) {
-      // rows and columns have the top index bit clear: the hypercube loses one dimension
-      const uint64_t topbit = (uint64_t)1 << (A->op.n - 1);
-      for (RowMask &rm : A->op.masks) {
-        DNM_CHECK(!(rm.mask & topbit), "internal: XParity mask reaches the top index bit");
-        for (RowTerm &t : rm.terms) t.sign &= ~topbit;
-      }
-      A->op.n -= 1;
-    }
-    PlanConfig cfg = plan_config_from_env();
-    if (const int fa = (flags >> DNM_MAT_AMIN_SHIFT) & 0xff) cfg.amin = fa;      // caller-chosen run length of window tiles
-    DNM_CHECK(A->left.host.swz == A->right.host.swz, "left and right vectors of a Full/Parity pair must share a layout");
-    cfg.swz = A->left.host.swz;
-    if (cfg.logR < 0) {
-      // measured: in index order 16 rows per thread pay from 2^26 local amplitudes on (profiles/r01_sweep6.txt);
-      // with swizzled vectors 8 rows beat 16 at every size (profiles/r02_exp3_v2.txt), and once the window pass
-      // runs first and the accumulating pass carries the diagonal, 4 rows per thread (two 1024-thread workgroups,
-      // 32 waves per CU) beat 8: L=30 16.9 -> 16.5 ms, 2-3 % from 2^26 amplitudes on
-      // (profiles/r02_exp46_rows4_series.txt, r02_exp47_rows4_sizes.txt)
-      int nl = A->op.n;
-      for (int r = A->nranks; r > 1; r >>= 1) --nl;
-      cfg.logR = cfg.swz ? 2 : (nl >= 26 ? 4 : 3);
-    }
-    if (cfg.diag_last < 0) cfg.diag_last = cfg.swz ? 1 : 0;
-    if (cfg.window_first < 0) {
-      // which pass writes y and which adds to it: the window pass is bound by its bytes (48 B/amp when it
-      // accumulates, at the streaming rate), the contiguous pass by its records (8.0 ms for 32.9 B/amp) -- so the y
-      // read belongs to the latter.  With swizzled vectors (in index order the window pass's gathers do not merge
-      // and it is the slow one either way, profiles/r01_prof_multi18.txt): L=30 17.5 -> 17.0 ms, L=28 4.43 -> 4.22,
-      // L=26 1.09 -> 1.07; level or worse while both vectors fit in the Infinity Cache
-      // (profiles/r02_exp41_pass_order.txt, r02_exp42_window_first_wide.txt)
-      int nl = A->op.n;
-      for (int r = A->nranks; r > 1; r >>= 1) --nl;
-      cfg.window_first = (cfg.swz && nl >= 25) ? 1 : 0;
-    }
-    if (!tile_config_supported(cfg.B, cfg.logR)) {
-      set_error("unsupported tile configuration B=%d logR=%d", cfg.B, cfg.logR);
-      return 1;
-    }
-    DNM_TRY(make_plan(A->op, A->rank, A->nranks, cfg, &A->plan));
-    if (flags & DNM_MAT_FORCE_GATHER) A->plan.use_tiled = false;
-    DNM_CHECK(!A->real_packed || A->plan.use_tiled, "real-packed operators run on the tiled kernel only (vector too small)");
-    if (A->nranks > 1 && !A->plan.use_tiled) {
-      // blocks smaller than one tile (or DNM_MAT_FORCE_GATHER): the window partition of the row kernel
-      A->plan.remote.clear();
-      A->plan.sends.clear();
-    }
-    if (A->plan.use_tiled) {
-      DNM_TRY(build_passes(*A, A->plan.local, &A->local_passes));
-      DNM_TRY(build_passes(*A, A->plan.remote, &A->remote_passes));
-      // flip-flop records (plan.h: DevFlip): decided for the operator as a whole, from its passes as they stand
-      decide_flip_bonds(A.get());
-      for (size_t i = 0; i < A->plan.local.size(); ++i)
-        DNM_TRY(build_flip_pass(*A, A->plan.local[i], A->local_passes[i].get()));
-      // the diagonal of what the kernel runs on as tables (DevPass::dblock), where it qualifies
-      for (auto *v : {&A->local_passes, &A->remote_passes})
-        for (auto &p : *v) DNM_TRY(build_diag_tables(*A, p.get()));
-      if (!A->host_only)
-        for (auto *v : {&A->local_passes, &A->remote_passes})
-          for (auto &p : *v) DNM_TRY(p->runs().upload());
-    }
-  }
+  DNM_TRY(setup_row_tables(A.get(), scm));
+  if (A->use_sc3) DNM_TRY(setup_sc3(A.get(), left, right, scm));
+  else DNM_CHECK(!(flags & DNM_MAT_REAL_PACKED) || A->hypercube,
+                 "real-packed operators: Full / Parity pairs, or a SpinConserve pair in the internal layout");
+  if (A->hypercube) DNM_TRY(setup_hypercube(A.get()));
+  // the kernel family the handle multiplies on (mat.h: Route), now that the knobs have had their say; a host-only
+  // handle has built no block-kernel table, so its SpinConserve pair in reference order reads as the row kernel
+  if (A->hypercube && A->plan.use_tiled) A->route = Route::Tiled;
+  else if (A->use_sc3) A->route = A->sc3->tiled ? Route::Sc3Tiled : Route::Sc3Rows;
+  else if (A->sc_pair) A->route = A->scblock.lb ? Route::ScBlock : Route::ScRows;
+  else A->route = Route::Gather;
   *out = A.release();
   return 0;
 }
@@ -713,7 +721,7 @@ int dnm_mat_set_exchange(dnm_mat *A, int scheme, int *chosen) {
   const int P = A->nranks;
   if (scheme == DNM_EXCHANGE_PARTNER || P < 2 || (scheme == DNM_EXCHANGE_AUTO && P < 4)) return 0;
   const SubView &lh = A->left.host, &rh = A->right.host;
-  if (!(A->hypercube && A->plan.use_tiled && !A->xparity && lh.type == rh.type && lh.L == rh.L &&
+  if (!(A->route == Route::Tiled && !A->xparity && lh.type == rh.type && lh.L == rh.L &&
         (lh.type == DNM_FULL || lh.space == rh.space) && lh.swz == rh.swz))
     return 0;
   int p = 0;
@@ -773,7 +781,7 @@ int dnm_mat_set_exchange(dnm_mat *A, int scheme, int *chosen) {
     int ns_ = 0, nr_ = 0;
     if (rc == 0) rc = dnm_mat_exchange_plan(made[which], &ns_, nullptr, &nr_, nullptr);
     if (rc == 0 && (ns_ || nr_)) { set_error("transposed exchange: a pass is not rank-local"); rc = 1; }
-    if (rc == 0 && !(made[which]->hypercube && made[which]->plan.use_tiled)) {
+    if (rc == 0 && made[which]->route != Route::Tiled) {
       set_error("transposed exchange: a part of the operator has no tiled plan"); rc = 1;
     }
     if (rc != 0) { delete made[0]; delete made[1]; return rc; }
@@ -825,30 +833,6 @@ int dnm_mat_is_real_packed(const dnm_mat *A, int *packed) {
   return 0;
 }
 
-// y = A x (- b z + c z2) in the SpinConserve internal layout; dot3 != null: the fused sums (device partials reduced here)
-static int sc3_mult(dnm_mat *A, const void *x, void *y, const void *z, double b, const void *z2, double c_re, double c_im,
-                    double *dot3_host, void *stream, int64_t win_start = -1, int phase = 0) {
-  Sc3Call call;
-  call.row0 = A->sc3->row0;
-  call.win_start = win_start >= 0 ? win_start : A->sc3->row0;     // one rank: x is the whole vector
-  call.zinit = (const double2 *)z;
-  call.zscale = b;
-  call.zinit2 = (const double2 *)z2;
-  call.z2re = c_re;
-  call.z2im = c_im;
-  const double *dg = A->have_diag ? (const double *)A->diag.p : nullptr;
-  if (!dot3_host) return launch_sc3(*A->sc3, A->dmsc_sc3, call, dg, x, y, S(stream), phase);
-  const size_t nwg = sc3_dot_partials(*A->sc3);
-  double *part = nullptr;
-  DNM_TRY(vec_scratch(((nwg + 1) * 3 + vk_reduce_scratch(3)) * sizeof(double), &part));
-  call.dot_out = part;
-  DNM_TRY(launch_sc3(*A->sc3, A->dmsc_sc3, call, dg, x, y, S(stream)));
-  DNM_TRY(vk_reduce_partials(part, (int)nwg, 3, part + 3 * nwg, S(stream), part + 3 * nwg + 3));
-  DNM_HIP(hipMemcpyAsync(dot3_host, part + 3 * nwg, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
-  DNM_HIP(hipStreamSynchronize(S(stream)));
-  return 0;
-}
-
 int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream) {
   DNM_CHECK(A && !A->host_only, "null or host-only matrix");
   DNM_CHECK(!A->real_packed || (A->use_sc3 && A->sc3->diag_mode == 1),
@@ -856,7 +840,7 @@ int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream) {
   // only when the first mask is the identity (bpetsc_template_1.c:177-180) and
   // left == right (operators.py:627-629; the caller guarantees it)
   if (A->masks.empty() || A->masks[0] != 0) return 0;
-  DNM_CHECK(A->nranks == 1 || !(A->hypercube && A->plan.use_tiled),
+  DNM_CHECK(A->nranks == 1 || A->route != Route::Tiled,
             "precomputed diagonal is not used by the partitioned tiled multiply");
   DNM_CHECK(A->M == A->N, "precompute_diagonal needs a square matrix");
   if (A->use_sc3) {
@@ -893,272 +877,11 @@ int dnm_mat_get_diagonal(dnm_mat *A, double *diag_host, void *stream) {
   return dnm_memcpy_d2h(diag_host, A->diag.p, (size_t)A->m_local * sizeof(double), stream);
 }
 
-// SpinConserve block kernel: the launch covers the high parts of the rows this rank owns.
-static int launch_sc(dnm_mat *A, int64_t win_start, int64_t win_len, const void *xw, void *y, void *stream) {
-  const double *dg = A->have_diag ? (const double *)A->diag.p : nullptr;
-  if (A->scblock.lb)
-    return launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, A->scblock, A->right.dev, A->m_local, A->row0,
-                           win_start, win_len, dg, xw, y, S(stream));
-  return launch_sc_matvec(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, A->row0,
-                          win_start, dg, xw, y, nullptr, S(stream));
-}
-
-int dnm_mat_mult_local(dnm_mat *A, const void *x, void *y, void *stream) {
-  DNM_CHECK(A && x && y, "null argument");
-  DNM_CHECK(!A->host_only, "host-only handle cannot multiply");
-  DNM_CHECK(x != y, "x and y must be different vectors");
-  if (A->hypercube && A->plan.use_tiled) {
-    for (auto &p : A->local_passes)
-      DNM_TRY(launch_pass(A, *p, PassCall(), x, y, nullptr, S(stream)));
-    return 0;
-  }
-  DNM_CHECK(A->nranks == 1, "this subspace pair cannot run partitioned (use dnm_mat_mult_window)");
-  if (A->use_sc3) return sc3_mult(A, x, y, nullptr, 0.0, nullptr, 0.0, 0.0, nullptr, stream);
-  if (A->sc_pair) return launch_sc(A, 0, A->N, x, y, stream);
-  return launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, A->M,
-                              A->have_diag ? (const double *)A->diag.p : nullptr, x, y, S(stream));
-}
-
-// The rank-local passes over ONE of nparts equal ranges of their workgroups (block ids [part, part + 1) * grid / nparts):
-// with an LDS-only plan whose tile holds the top index bits, range `part` reads and writes exactly the amplitudes whose
-// highest non-tile index bits equal `part` -- the transposed exchange runs its layout-B pass sub-piece by sub-piece.
-int dnm_mat_mult_local_part(dnm_mat *A, const void *x, void *y, int part, int nparts, void *stream) {
-  DNM_CHECK(A && x && y && x != y && !A->host_only, "bad argument");
-  DNM_CHECK(A->hypercube && A->plan.use_tiled, "only the tiled hypercube passes run over a range of their workgroups");
-  DNM_CHECK(nparts >= 1 && (nparts & (nparts - 1)) == 0 && part >= 0 && part < nparts, "bad range %d of %d", part, nparts);
-  for (auto &p : A->local_passes) {
-    const unsigned grid = 1u << (p->n_eff - p->whole.desc.tile_bits);
-    DNM_CHECK((unsigned)nparts <= grid, "more ranges than workgroups");
-    PassCall c;
-    c.block_offset = (uint32_t)part * (grid / (unsigned)nparts);
-    c.nparts = (unsigned)nparts;
-    DNM_TRY(launch_pass(A, *p, c, x, y, nullptr, S(stream)));
-  }
-  return 0;
-}
-
-// what the top non-tile index bits of the rank-local passes are: *top_free_bit = the highest index bit that is in no
-// pass's tile (the ranges of dnm_mat_mult_local_part split along it and the ones below it), -1 if passes disagree
-int dnm_mat_local_part_bits(const dnm_mat *A, int *top_free_bit, int *gathers) {
-  DNM_CHECK(A && top_free_bit && gathers, "null argument");
-  *top_free_bit = -1;
-  *gathers = 0;
-  if (!(A->hypercube && A->plan.use_tiled)) return 0;
-  int top = -2;
-  for (auto &p : A->local_passes) {
-    uint64_t tb = 0;
-    const DevPass &d = p->whole.desc;
-    for (int j = 0; j < d.nseg; ++j) tb |= ((((uint64_t)1 << d.seg_len[j]) - 1) << d.seg_pos[j]);
-    int hi = p->n_eff - 1;
-    while (hi >= 0 && ((tb >> hi) & 1)) --hi;
-    if (top == -2) top = hi; else if (top != hi) top = -1;
-    *gathers += (int)(d.loop[LP_COUNT] - d.loop[LP_GATHER_REAL]);     // gathered records
-    *gathers += (int)(d.tab_loop[2] - d.tab_loop[1]);
-  }
-  *top_free_bit = top < 0 ? -1 : top;
-  return 0;
-}
-
-// The handles whose one-rank multiply is a single launch of a one-thread-per-row kernel (launch_gather_matvec, or
-// launch_sc_matvec when the SpinConserve block kernel is off): Explicit / Auto, projections, SpinConserve in reference
-// order below the block kernel's sizes, XParity on those, Full / Parity under DNM_MAT_FORCE_GATHER.  Their fused twins
-// (row_fused_kernels.hip) take the recurrence's start vectors and the Lanczos sums.  DNM_ROW_FUSE=0 (experiments, read
-// when the handle is created): the multiply and separate sweeps, as before the twins existed -- the A/B switch of
-// profiles/interior_eigsolve.txt.
-static bool row_kernel_fuses(const dnm_mat *A) {
-  if (A->host_only || A->nranks != 1 || A->use_sc3 || !A->remote_passes.empty()) return false;
-  if (A->hypercube && A->plan.use_tiled) return false;
-  if (A->sc_pair && A->scblock.lb) return false;
-  return A->row_fuse;
-}
-
-static int launch_row_fused(dnm_mat *A, const void *x, void *y, const RowFuse &f, void *stream) {
-  const double *dg = A->have_diag ? (const double *)A->diag.p : nullptr;
-  if (A->sc_pair)
-    return launch_sc_matvec_fused(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, dg, x, y,
-                                  f, S(stream));
-  return launch_gather_matvec_fused(A->dmsc, A->left.dev, A->right.dev, A->M, dg, x, y, f, S(stream));
-}
-
-// y = A x - b z, <x, y> = sum conj(x_i) y_i and |y|^2 (z may be null).  When the plan is tiled, the first pass
-// starts its accumulators from -b z instead of zero and the last pass -- if it stages x in LDS -- accumulates the
-// sums (per-workgroup partials, summed by a second tiny kernel); otherwise one fused sweep does the same.
-int dnm_mat_mult_lanczos(dnm_mat *A, const void *x, void *y, const void *z, double b, double *dot, void *stream) {
-  DNM_CHECK(A && x && y && dot, "null argument");
-  DNM_CHECK(A->remote_passes.empty(), "operator couples different ranks: no fused Lanczos step");
-  DNM_CHECK(z != y && x != y, "y must not alias x or z");
-  const bool tiled = A->hypercube && A->plan.use_tiled && !A->local_passes.empty() && !A->host_only;
-  if (A->use_sc3 && !A->host_only) {
-    if (A->sc3->tiled) return sc3_mult(A, x, y, z, b, nullptr, 0.0, 0.0, dot, stream);
-    DNM_TRY(sc3_mult(A, x, y, z, b, nullptr, 0.0, 0.0, nullptr, stream));       // the row kernel takes the start vector
-    return vec_lanczos_dot_host(y, nullptr, x, A->m_local, 0.0, dot, S(stream));
-  }
-  if (!tiled && A->sc_pair && A->scblock.lb && A->nranks == 1 && !A->host_only) {
-    // SpinConserve block kernel: the beta term starts the accumulators, the sums are taken while the block of x
-    // is still in LDS
-    const size_t nwg = (size_t)sc_block_grid(A->scblock);
-    double *part = nullptr;
-    DNM_TRY(vec_scratch((nwg + 1) * 3 * sizeof(double), &part));
-    DNM_TRY(launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, A->scblock, A->right.dev, A->m_local, A->row0, 0,
-                            A->N, A->have_diag ? (const double *)A->diag.p : nullptr, x, y, S(stream), z, b, part));
-    DNM_TRY(vk_reduce_partials(part, (int)nwg, 3, part + 3 * nwg, S(stream)));
-    DNM_HIP(hipMemcpyAsync(dot, part + 3 * nwg, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
-    DNM_HIP(hipStreamSynchronize(S(stream)));
-    return 0;
-  }
-  if (!tiled && row_kernel_fuses(A) && A->M == A->N && A->left.host.swz == A->right.host.swz) {
-    // one thread per row: the beta term joins the row's sum before the store, the sums leave as workgroup partials
-    const size_t nwg = (size_t)(A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local));
-    double *part = nullptr;
-    DNM_TRY(vec_scratch(((nwg + 1) * 3 + vk_reduce_scratch(3)) * sizeof(double), &part));
-    RowFuse f;
-    f.zinit = z;
-    f.zscale = b;
-    f.dot_out = part;
-    DNM_TRY(launch_row_fused(A, x, y, f, stream));
-    DNM_TRY(vk_reduce_partials(part, (int)nwg, 3, part + 3 * nwg, S(stream), part + 3 * nwg + 3));
-    DNM_HIP(hipMemcpyAsync(dot, part + 3 * nwg, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
-    DNM_HIP(hipStreamSynchronize(S(stream)));
-    return 0;
-  }
-  if (!tiled) {
-    DNM_TRY(dnm_mat_mult_local(A, x, y, stream));
-    return vec_lanczos_dot_host(y, z, x, A->m_local, b, dot, S(stream));
-  }
-  const bool fused_dot = A->local_passes.back()->whole.desc.need_tile != 0;
-  const size_t nblk = pass_dot_partials(A, *A->local_passes.back());
-  double *part = nullptr;
-  if (fused_dot) DNM_TRY(vec_scratch(((nblk + 1) * 3 + vk_reduce_scratch(3)) * sizeof(double), &part));
-  for (size_t i = 0; i < A->local_passes.size(); ++i) {
-    PassCall c;
-    if (i == 0 && z) {
-      DNM_CHECK(!A->local_passes[i]->whole.desc.accumulate, "internal: first pass accumulates");
-      c.zinit = z;
-      c.zscale = b;
-    }
-    if (fused_dot && i + 1 == A->local_passes.size()) c.dot_out = part;
-    DNM_TRY(launch_pass(A, *A->local_passes[i], c, x, y, nullptr, S(stream)));
-  }
-  if (!fused_dot) return vec_lanczos_dot_host(y, nullptr, x, A->m_local, 0.0, dot, S(stream));
-  DNM_TRY(vk_reduce_partials(part, (int)nblk, 3, part + 3 * nblk, S(stream), part + 3 * nblk + 3));
-  DNM_HIP(hipMemcpyAsync(dot, part + 3 * nblk, 3 * sizeof(double), hipMemcpyDeviceToHost, S(stream)));
-  DNM_HIP(hipStreamSynchronize(S(stream)));
-  return 0;
-}
-
-// true when the multiply can start its accumulators from other vectors (dnm_mat_mult_sub2 costs no extra sweep)
-int dnm_mat_fuses_init(const dnm_mat *A) {
-  if (!A || A->host_only || !A->remote_passes.empty()) return 0;
-  if (A->hypercube && A->plan.use_tiled && !A->local_passes.empty()) return 1;
-  if (A->use_sc3) return 1;
-  if (A->sc_pair && A->scblock.lb && A->nranks == 1) return 1;
-  return row_kernel_fuses(A) ? 1 : 0;
-}
-
-// y = A x - b z + c z2 without the sums (Chebyshev / Clenshaw recurrences; z2 may be null): the extra terms ride
-// on the multiply where a kernel can start its accumulators from them, otherwise one more sweep each.
-int dnm_mat_mult_sub2(dnm_mat *A, const void *x, void *y, const void *z, double b, const void *z2, double c_re,
-                      double c_im, void *stream) {
-  DNM_CHECK(A && x && y && z, "null argument");
-  DNM_CHECK(A->remote_passes.empty(), "operator couples different ranks: use the partitioned multiply");
-  DNM_CHECK(z != y && x != y && z2 != y, "y must not alias x, z or z2");
-  DNM_CHECK(!A->host_only, "host-only handle cannot multiply");
-  if (A->hypercube && A->plan.use_tiled && !A->local_passes.empty()) {
-    for (size_t i = 0; i < A->local_passes.size(); ++i) {
-      PassCall c;
-      if (i == 0) {
-        DNM_CHECK(!A->local_passes[i]->whole.desc.accumulate, "internal: first pass accumulates");
-        c.zinit = z;
-        c.zscale = b;
-        c.zinit2 = z2;
-        c.z2re = c_re;
-        c.z2im = c_im;
-      }
-      DNM_TRY(launch_pass(A, *A->local_passes[i], c, x, y, nullptr, S(stream)));
-    }
-    return 0;
-  }
-  if (A->use_sc3) return sc3_mult(A, x, y, z, b, z2, c_re, c_im, nullptr, stream);
-  if (A->sc_pair && A->scblock.lb && A->nranks == 1)
-    return launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, A->scblock, A->right.dev, A->m_local, A->row0, 0,
-                           A->N, A->have_diag ? (const double *)A->diag.p : nullptr, x, y, S(stream), z, b, nullptr,
-                           z2, c_re, c_im);
-  if (row_kernel_fuses(A)) {
-    RowFuse f;
-    f.zinit = z;
-    f.zscale = b;
-    f.zinit2 = z2;
-    f.z2re = c_re;
-    f.z2im = c_im;
-    return launch_row_fused(A, x, y, f, stream);
-  }
-  DNM_TRY(dnm_mat_mult_local(A, x, y, stream));
-  DNM_TRY(vk_axpby(y, z, A->m_local, -b, 0.0, 1.0, 0.0, S(stream)));
-  if (z2) DNM_TRY(vk_axpby(y, z2, A->m_local, c_re, c_im, 1.0, 0.0, S(stream)));
-  return 0;
-}
-
-int dnm_mat_mult_sub(dnm_mat *A, const void *x, void *y, const void *z, double b, void *stream) {
-  return dnm_mat_mult_sub2(A, x, y, z, b, nullptr, 0.0, 0.0, stream);
-}
-
-int dnm_mat_mult_dot(dnm_mat *A, const void *x, void *y, double *dot, void *stream) {
-  DNM_CHECK(dot, "null argument");
-  double d3[3];
-  DNM_TRY(dnm_mat_mult_lanczos(A, x, y, nullptr, 0.0, d3, stream));
-  dot[0] = d3[0];
-  dot[1] = d3[1];
-  return 0;
-}
-
-int dnm_mat_mult(dnm_mat *A, const void *x, void *y, void *stream) {
-  DNM_CHECK(A, "null matrix");
-  DNM_CHECK(A->remote_passes.empty(),
-            "operator couples different ranks: use dnm_mat_mult_local + dnm_mat_mult_remote");
-  return dnm_mat_mult_local(A, x, y, stream);
-}
-
 int dnm_mat_ownership(const dnm_mat *A, int64_t *row0, int64_t *m_local) {
   DNM_CHECK(A, "null matrix");
   // (internal SpinConserve layout: the rank's range of the layout -- the index space its windows are expressed in)
   if (row0) *row0 = A->use_sc3 ? (A->real_packed ? A->sc3->row0 / 2 : A->sc3->row0) : A->row0;
   if (m_local) *m_local = A->m_local;
-  return 0;
-}
-
-int dnm_mat_column_window(dnm_mat *A, int64_t *cmin, int64_t *cmax, void *stream) {
-  DNM_CHECK(A && cmin && cmax, "bad argument");
-  if (A->use_sc3) {          // positions of the internal layout, from the T blocks the rank's rows reach (host tables)
-    A->sc3->window(cmin, cmax);
-    if (A->real_packed) {     // whole blocks: [cmin, cmax + 1) is a range of pairs
-      *cmin /= 2;
-      *cmax = (*cmax + 1) / 2 - 1;
-    }
-    return 0;
-  }
-  DNM_CHECK(!A->host_only, "bad argument");
-  DNM_CHECK(!(A->hypercube && A->plan.use_tiled), "Full/Parity partitions on 2^p ranks exchange partner blocks, not windows");
-  if (A->win_max < A->win_min) {
-    const int nb = A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local);
-    DevBuf buf;
-    DNM_TRY(buf.alloc((size_t)nb * 2 * sizeof(int64_t)));
-    if (A->sc_pair)
-      DNM_TRY(launch_sc_matvec(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, A->row0,
-                               0, nullptr, nullptr, nullptr, (int64_t *)buf.p, S(stream)));
-    else
-      DNM_TRY(launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, A->m_local, nullptr, nullptr, nullptr,
-                                   S(stream), A->row0, 0, 0, (int64_t *)buf.p));
-    std::vector<int64_t> h((size_t)nb * 2);
-    DNM_TRY(dnm_memcpy_d2h(h.data(), buf.p, h.size() * sizeof(int64_t), stream));
-    // (a SpinConserve pair always reads its own rows' columns; a general pair reads what its masks reach)
-    int64_t lo = A->sc_pair ? A->row0 : INT64_MAX, hi = A->sc_pair ? A->row0 + A->m_local - 1 : INT64_MIN;
-    for (int b = 0; b < nb; ++b) { lo = std::min(lo, h[2 * b]); hi = std::max(hi, h[2 * b + 1]); }
-    if (hi < lo) lo = hi = 0;          // no matrix element at all in these rows
-    A->win_min = lo;
-    A->win_max = hi;
-  }
-  *cmin = A->win_min;
-  *cmax = A->win_max;
   return 0;
 }
 
@@ -1176,158 +899,6 @@ int dnm_mat_column_ranges(dnm_mat *A, int64_t max_ranges, int64_t *ranges, int64
   return 0;
 }
 
-int dnm_mat_column_chunks(dnm_mat *A, int chunk_shift, uint8_t *map, int64_t nchunks, void *stream) {
-  DNM_CHECK(A && map && chunk_shift >= 0 && chunk_shift < 62, "bad argument");
-  int64_t lo, hi;
-  DNM_TRY(dnm_mat_column_window(A, &lo, &hi, stream));
-  const int64_t first = lo >> chunk_shift;
-  DNM_CHECK(nchunks == (hi >> chunk_shift) - first + 1, "the window [%lld, %lld] has %lld chunks of 2^%d columns",
-            (long long)lo, (long long)hi, (long long)((hi >> chunk_shift) - first + 1), chunk_shift);
-  if (A->use_sc3) {
-    A->sc3->chunks(chunk_shift + (A->real_packed ? 1 : 0), first, nchunks, map);      // (chunks of 2^shift elements)
-    return 0;
-  }
-  const int nb = A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local);
-  DevBuf range, dmap;
-  DNM_TRY(range.alloc((size_t)nb * 2 * sizeof(int64_t)));
-  DNM_TRY(dmap.alloc((size_t)nchunks));
-  DNM_HIP(hipMemsetAsync(dmap.p, 0, (size_t)nchunks, S(stream)));
-  ColMark mark;
-  mark.map = (uint8_t *)dmap.p;
-  mark.shift = chunk_shift;
-  mark.first = first;
-  if (A->sc_pair)
-    DNM_TRY(launch_sc_matvec(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, A->row0,
-                             0, nullptr, nullptr, nullptr, (int64_t *)range.p, S(stream), mark));
-  else
-    DNM_TRY(launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, A->m_local, nullptr, nullptr, nullptr,
-                                 S(stream), A->row0, 0, 0, (int64_t *)range.p, mark));
-  DNM_TRY(dnm_memcpy_d2h(map, dmap.p, (size_t)nchunks, stream));
-  return 0;
-}
-
-int dnm_mat_mult_window(dnm_mat *A, const void *x_window, int64_t win_start, int64_t win_len, void *y_local,
-                        void *stream) {
-  DNM_CHECK(A && x_window && y_local && !A->host_only, "bad argument");
-  int64_t lo, hi;
-  DNM_TRY(dnm_mat_column_window(A, &lo, &hi, stream));
-  DNM_CHECK(win_start <= lo && win_start + win_len > hi,
-            "window [%lld, %lld) does not cover the columns [%lld, %lld] this rank reads", (long long)win_start,
-            (long long)(win_start + win_len), (long long)lo, (long long)hi);
-  if (A->use_sc3)
-    return sc3_mult(A, x_window, y_local, nullptr, 0.0, nullptr, 0.0, 0.0, nullptr, stream,
-                    A->real_packed ? 2 * win_start : win_start);
-  if (A->sc_pair) return launch_sc(A, win_start, win_len, x_window, y_local, stream);
-  // any other subspace pair: one thread per row, columns read from the window (index order)
-  return launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, A->m_local,
-                              A->have_diag ? (const double *)A->diag.p : nullptr, x_window, y_local, S(stream),
-                              A->row0, win_start, 0, nullptr);
-}
-
-// Rows of a window partition whose columns all lie in [col_lo, col_hi) -- the rank's own block of x: they can be
-// multiplied while the rest of the window is on the links.  From the per-workgroup column ranges of the row kernels
-// (one sweep): runs of consecutive workgroups that read nothing else, the largest `max_ranges` of them, none
-// shorter than min_blocks workgroups (of 256 rows).  ranges: pairs [r0, r1) of local row numbers, ascending.
-int dnm_mat_window_local_rows(dnm_mat *A, int64_t col_lo, int64_t col_hi, int max_ranges, int min_blocks,
-                              int64_t *ranges, int *nranges, void *stream) {
-  DNM_CHECK(A && ranges && nranges && max_ranges >= 1, "bad argument");
-  *nranges = 0;
-  if (A->use_sc3 || A->host_only || (A->hypercube && A->plan.use_tiled) || A->m_local <= 0) return 0;
-  if (A->left.host.swz != 0) return 0;       // a swizzled result block is not a sequence of row ranges
-  DNM_CHECK(A->row0 >= 0, "internal: no first row in reference order");      // (the sweep below walks reference rows)
-  const int64_t per = A->sc_pair ? sc_rows_per_block() : gather_rows_per_block();
-  const int nb = A->sc_pair ? sc_num_blocks(A->m_local) : gather_num_blocks(A->m_local);
-  DevBuf buf;
-  DNM_TRY(buf.alloc((size_t)nb * 2 * sizeof(int64_t)));
-  if (A->sc_pair)
-    DNM_TRY(launch_sc_matvec(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, A->m_local, A->row0,
-                             0, nullptr, nullptr, nullptr, (int64_t *)buf.p, S(stream)));
-  else
-    DNM_TRY(launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, A->m_local, nullptr, nullptr, nullptr,
-                                 S(stream), A->row0, 0, 0, (int64_t *)buf.p));
-  std::vector<int64_t> h((size_t)nb * 2);
-  DNM_TRY(dnm_memcpy_d2h(h.data(), buf.p, h.size() * sizeof(int64_t), stream));
-  // (a SpinConserve pair reads its own rows' columns as well: the diagonal and the row's own amplitude)
-  struct Run { int64_t b0, b1; };
-  std::vector<Run> runs;
-  for (int b = 0; b < nb;) {
-    auto local = [&](int i) {
-      int64_t lo = h[2 * (size_t)i], hi = h[2 * (size_t)i + 1];
-      if (A->sc_pair) {
-        lo = std::min(lo, A->row0 + (int64_t)i * per);
-        hi = std::max(hi, std::min(A->row0 + A->m_local, A->row0 + (int64_t)(i + 1) * per) - 1);
-      }
-      return hi < lo || (lo >= col_lo && hi < col_hi);
-    };
-    if (!local(b)) { ++b; continue; }
-    int e = b;
-    while (e < nb && local(e)) ++e;
-    if (e - b >= std::max(1, min_blocks)) runs.push_back({b, e});
-    b = e;
-  }
-  std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.b1 - a.b0 > b.b1 - b.b0; });
-  if ((int)runs.size() > max_ranges) runs.resize((size_t)max_ranges);
-  std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.b0 < b.b0; });
-  for (const Run &r : runs) {
-    ranges[2 * *nranges] = r.b0 * per;
-    ranges[2 * *nranges + 1] = std::min(A->m_local, r.b1 * per);
-    ++*nranges;
-  }
-  return 0;
-}
-
-// dnm_mat_mult_window for the local rows [r0, r1) only (y_local is still the rank's whole result block)
-int dnm_mat_mult_window_rows(dnm_mat *A, const void *x_window, int64_t win_start, int64_t win_len, void *y_local,
-                             int64_t r0, int64_t r1, void *stream) {
-  DNM_CHECK(A && x_window && y_local && !A->host_only, "bad argument");
-  DNM_CHECK(!A->use_sc3 && !(A->hypercube && A->plan.use_tiled), "this operator does not multiply by row ranges");
-  DNM_CHECK(r0 >= 0 && r0 < r1 && r1 <= A->m_local, "row range [%lld, %lld) outside the %lld local rows", (long long)r0,
-            (long long)r1, (long long)A->m_local);
-  const double *dg = A->have_diag ? (const double *)A->diag.p + r0 : nullptr;
-  char *y = (char *)y_local + (size_t)r0 * 16;
-  if (A->sc_pair && A->scblock.lb) {
-    ScBlock blk = A->scblock;
-    blk.h_first = sub_i2s(A->row0 + r0, A->left.host) >> blk.lb;
-    blk.h_last = sub_i2s(A->row0 + r1 - 1, A->left.host) >> blk.lb;
-    blk.swizzle = 0;
-    blk.perm = nullptr;
-    blk.nperm = 0;
-    return launch_sc_block(A->dmsc, (const ScMask *)A->d_scmasks.p, blk, A->right.dev, r1 - r0, A->row0 + r0, win_start,
-                           win_len, dg, x_window, y, S(stream));
-  }
-  if (A->sc_pair)
-    return launch_sc_matvec(A->dmsc, (const ScMask *)A->d_scmasks.p, A->sclow, A->right.dev, r1 - r0, A->row0 + r0,
-                            win_start, dg, x_window, y, nullptr, S(stream));
-  return launch_gather_matvec(A->dmsc, A->left.dev, A->right.dev, r1 - r0, dg, x_window, y, S(stream), A->row0 + r0,
-                              win_start, 0, nullptr);
-}
-
-int dnm_mat_window_split(const dnm_mat *A, int *supported) {
-  DNM_CHECK(A && supported, "null argument");
-  *supported = (A->use_sc3 && A->sc3->tiled && !A->sc3->graph && A->nranks > 1) ? 1 : 0;    // (a bond graph's lo pass reads other blocks)
-  return 0;
-}
-
-int dnm_mat_mult_window_local(dnm_mat *A, const void *x_local, void *y_local, void *stream) {
-  DNM_CHECK(A && x_local && y_local && !A->host_only, "bad argument");
-  DNM_CHECK(A->use_sc3 && A->sc3->tiled, "this operator's window multiply does not split (dnm_mat_window_split)");
-  // the lo pass reads the rank's own rows and, for the Lo/W boundary bond, other rows of the same T block: all local
-  return sc3_mult(A, x_local, y_local, nullptr, 0.0, nullptr, 0.0, 0.0, nullptr, stream, A->sc3->row0, 1);
-}
-
-int dnm_mat_mult_window_remote(dnm_mat *A, const void *x_window, int64_t win_start, int64_t win_len, void *y_local,
-                               void *stream) {
-  DNM_CHECK(A && x_window && y_local && !A->host_only, "bad argument");
-  DNM_CHECK(A->use_sc3 && A->sc3->tiled, "this operator's window multiply does not split (dnm_mat_window_split)");
-  int64_t lo, hi;
-  DNM_TRY(dnm_mat_column_window(A, &lo, &hi, stream));
-  DNM_CHECK(win_start <= lo && win_start + win_len > hi,
-            "window [%lld, %lld) does not cover the positions [%lld, %lld] this rank reads", (long long)win_start,
-            (long long)(win_start + win_len), (long long)lo, (long long)hi);
-  return sc3_mult(A, x_window, y_local, nullptr, 0.0, nullptr, 0.0, 0.0, nullptr, stream,
-                  A->real_packed ? 2 * win_start : win_start, 2);
-}
-
 int dnm_mat_exchange_plan(const dnm_mat *A, int *nsend, dnm_xfer *sends, int *nrecv, dnm_xfer *recvs) {
   DNM_CHECK(A && nsend && nrecv, "null argument");
   *nsend = (int)A->plan.sends.size();
@@ -1341,15 +912,6 @@ int dnm_mat_exchange_plan(const dnm_mat *A, int *nsend, dnm_xfer *sends, int *nr
       recvs[i] = {p->partner, (int32_t)i, p->src_off, (int64_t)1 << p->n_eff};
     }
   return 0;
-}
-
-int dnm_mat_mult_remote(dnm_mat *A, int32_t recv_index, const void *x_recv, void *y, void *stream) {
-  DNM_CHECK(A && x_recv && y, "null argument");
-  DNM_CHECK(!A->host_only, "host-only handle cannot multiply");
-  DNM_CHECK(recv_index >= 0 && recv_index < (int)A->remote_passes.size(), "rank %d has no receive %d", A->rank,
-            recv_index);
-  const auto &p = A->remote_passes[recv_index];
-  return launch_pass(A, *p, PassCall(), x_recv, (char *)y + (size_t)p->y_off * 16, x_recv, S(stream));
 }
 
 int dnm_mat_norm_inf(dnm_mat *A, double *nrm, void *stream) {
@@ -1439,7 +1001,7 @@ int dnm_mat_plan_describe(const dnm_mat *A, char *buf, size_t buflen) {
   else s = A->nranks > 1 ? "generic row-gather kernel (rows split in index order, columns through a window)\n"
                          : "generic row-gather kernel (non-hypercube subspace pair)\n";
   if (A->hypercube && !A->plan.use_tiled) s += "generic row-gather kernel in use\n";
-  if (A->hypercube && A->plan.use_tiled) {
+  if (A->route == Route::Tiled) {
     // masks of many terms run as table records (plan.h: DevTab); said only when there are any: the plans without keep their text
     size_t ntab = 0, nquad = 0;
     for (const auto &p : A->local_passes) { ntab += p->whole.tabs.size(); nquad += p->whole.desc.loop[LP_COUNT] - p->whole.desc.loop[0]; }
@@ -1567,7 +1129,7 @@ int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_pas
   DNM_CHECK(A, "null matrix");
   if (n_local_passes) *n_local_passes = (int)A->local_passes.size();
   if (n_remote_passes) *n_remote_passes = (int)A->remote_passes.size();
-  if (tiled) *tiled = (A->hypercube && A->plan.use_tiled) ? 1 : 0;
+  if (tiled) *tiled = A->route == Route::Tiled ? 1 : 0;
   if (B) *B = A->plan.cfg.B;
   if (logR) *logR = A->plan.cfg.logR;
   if (n_loc) *n_loc = A->plan.n_loc;
@@ -1576,7 +1138,7 @@ int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_pas
 
 int dnm_mat_plan_launches(const dnm_mat *A, int *n) {
   DNM_CHECK(A && n, "null argument");
-  *n = (A->hypercube && A->plan.use_tiled) ? (int)A->local_passes.size() : 1;
+  *n = A->route == Route::Tiled ? (int)A->local_passes.size() : 1;
   return 0;
 }
 

@@ -63,6 +63,19 @@ struct FlipBond {
 
 int rdm_release_scratch();   // frees the cached scratch of dnm_reduced_density_matrix
 
+// The kernel family a handle's one-rank multiply runs on.  dnm_mat_create decides it last, after the knobs
+// (DNM_SC3_TILED, DNM_SC_BLOCK, DNM_ROW_FUSE, DNM_MAT_FORCE_GATHER) have had their say; nothing changes it afterwards.
+enum class Route {
+  Tiled,      // Full / Parity pair: the tiled hypercube passes
+  Sc3Tiled,   // SpinConserve pair in the internal layout (sc3.h): the two tiled passes
+  Sc3Rows,    // ... its row kernel
+  ScBlock,    // SpinConserve pair in reference order: one workgroup per block of low bits
+  ScRows,     // ... one thread per row
+  Gather,     // any other pair: one thread per row with index maps
+};
+// the last three sweep a range of rows in one launch (mat_mult.cpp: launch_rows) and can run behind a column window
+inline bool row_route(Route r) { return r == Route::ScBlock || r == Route::ScRows || r == Route::Gather; }
+
 }  // namespace dnm
 
 struct dnm_mat {
@@ -83,6 +96,7 @@ struct dnm_mat {
   int flags = 0;
   bool xparity = false;
   bool host_only = false;         // DNM_MAT_HOST_ONLY: plan and tables only, no device
+  dnm::Route route = dnm::Route::Gather;   // a host-only handle has the route its flags imply and refuses to launch
 
   bool hypercube = false;        // Full/Full or Parity/Parity: index space is a hypercube
   // DNM_MAT_REAL_PACKED: vectors are real, two amplitudes per complex128 element (M, N, m_local, n_local count
@@ -120,6 +134,37 @@ struct dnm_mat {
 
   dnm::DevBuf diag;              // cached diagonal (double[m_local]) if precomputed
   bool have_diag = false;
+  const double *cached_diag() const { return have_diag ? (const double *)diag.p : nullptr; }
   double nrm = -1.0;             // ctx->nrm cache, -1 = unset (bpetsc_template_2.c:926-929)
   dnm::DevBuf scratch;
 };
+
+namespace dnm {
+
+// What the route of a handle fuses into y = A x - b z + c z2 (mat_mult.cpp: mult_fused does the rest in sweeps).
+//   start: -b z + c z2 joins the kernel's accumulators (dnm_mat_fuses_init: the recurrence costs no extra sweep)
+//   sums:  <x, y> and |y|^2 leave the kernel as workgroup partials
+struct RouteFuses {
+  bool start = false, sums = false;
+};
+inline RouteFuses route_fuses(const dnm_mat &A) {
+  RouteFuses f;
+  if (A.host_only || !A.remote_passes.empty()) return f;     // nothing launches; nothing fused beside remote passes
+  switch (A.route) {
+    case Route::Tiled:        // the first pass starts from the vectors; the last takes the sums if it stages x (need_tile)
+      f.start = !A.local_passes.empty();
+      f.sums = f.start && A.local_passes.back()->whole.desc.need_tile != 0;
+      break;
+    case Route::Sc3Tiled: f.start = f.sums = true; break;
+    case Route::Sc3Rows: f.start = true; break;                // the row kernel takes the start vectors, not the sums
+    case Route::ScBlock: f.start = f.sums = A.nranks == 1; break;       // one rank only
+    case Route::ScRows:
+    case Route::Gather:       // the fused twins (row_fused.h): one rank only, and not under DNM_ROW_FUSE=0
+      f.start = A.nranks == 1 && A.row_fuse;
+      f.sums = f.start && A.M == A.N && A.left.host.swz == A.right.host.swz;      // x_row is x at the row's own index
+      break;
+  }
+  return f;
+}
+
+}  // namespace dnm
