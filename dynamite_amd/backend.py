@@ -1921,6 +1921,65 @@ def swap_moments(vec, subspace, bonds, xparity_sector=0):
     return out
 
 
+def _cycles_c(cycles):
+    cycles = np.ascontiguousarray(cycles, dtype=np.int32).reshape(-1, 3)
+    return cycles, cycles.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def cyc_moments_plan(sub_c, ncycles):
+    """``dnm_cyc_moments_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
+    launch, bytes of the partial tiles) of the three-site rotation sweep with ``ncycles`` triples over a state of the
+    subspace -- the bond-swap plan for the same number of columns."""
+    tr, pb, nw, lb, sb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_cyc_moments_plan(C.byref(sub_c), int(ncycles), C.byref(tr), C.byref(pb), C.byref(nw),
+                                               C.byref(lb), C.byref(sb)))
+    return tr.value, pb.value, nw.value, int(lb.value), int(sb.value)
+
+
+def cyc_partner_indices(sub_c, cycles, rows, xparity_sector=0):
+    """``dnm_cyc_partner_indices`` (host only): ``(idx, sign)``, int64 and int8 arrays (len(rows), len(cycles)) -- for
+    the row of index ``rows[n]`` of the vector and triple m = (a, b, c), the reference-order index into the vector of
+    that row's configuration with the three spins rotated (bit a from b, bit b from c, bit c from a), and its factor:
+    +1, or ``xparity_sector`` where the rotation sets bit L - 1 and the amplitude is the complement's."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    cycles, cp = _cycles_c(cycles)
+    idx = np.empty((rows.size, cycles.shape[0]), dtype=np.int64)
+    sign = np.empty((rows.size, cycles.shape[0]), dtype=np.int8)
+    _lib.check(_lib.lib().dnm_cyc_partner_indices(C.byref(sub_c), int(xparity_sector), cycles.shape[0], cp, rows.size,
+                                                  _lib.p64(rows), _lib.p64(idx),
+                                                  sign.ctypes.data_as(C.POINTER(C.c_int8))))
+    return idx, sign
+
+
+def cyc_moments(vec, subspace, cycles, xparity_sector=0):
+    """The raw three-site rotation moments of the state in ``vec`` in one pass: numpy array G of shape (n + 1, n + 1),
+    complex128, for the n <= 63 oriented triples ``cycles`` = [(a_0, b_0, c_0), ...] of pairwise distinct sites: G = A^H
+    A with A[r, 0] = psi(r) and A[r, 1 + m] = psi(r with bit a_m from b_m, bit b_m from c_m, bit c_m from a_m) = (C_m
+    psi)(r), C_m = P_ab P_bc, so that G[0, 0] = <psi|psi>, G[0, 1 + m] = <C_m> and G[1 + m, 1 + m'] = <C_m^H C_m'> (raw
+    sums, nothing normalised; G is Hermitian to the last bit).  sigma_a . (sigma_b x sigma_c) = 2i (C - C^H), and C^H is
+    the rotation of (a, c, b).  ``subspace`` is the descriptor of the Full, Parity or SpinConserve subspace of the
+    vector -- with ``xparity_sector`` = +-1 that of the parent of the XParity subspace whose representatives the vector
+    holds.  Swizzled Full / Parity vectors are read as they lie; a SpinConserve vector in the internal layout is
+    converted to reference order first (one extra vector).  The partners of a rank's rows lie on other ranks: on more
+    than one rank this raises ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('chirality moments of a partitioned state: the partner amplitudes of a rank\'s rows '
+                                  'lie on other ranks')
+    x, sub_c = _reference_order(vec, subspace['data'])
+    cycles, cp = _cycles_c(cycles)
+    n = cycles.shape[0]
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
+    expect = full.value // 2 if xparity_sector else full.value
+    if x.numel() != expect:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), expect))
+    out = np.empty((n + 1, n + 1), dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_cyc_moments(C.c_void_p(x.data_ptr()), C.byref(sub_c), int(xparity_sector), n, cp,
+                                          out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return out
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

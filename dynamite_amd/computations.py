@@ -709,15 +709,15 @@ _SWAP_CALL_MAX = 63       # bonds of one call of backend.swap_moments
 _SWAP_CHUNK = 31          # longer lists: chunks of this size, one call per pair of chunks on their union
 
 
-def _swap_subspace(state):
-    """(descriptor's subspace, XParity sector or 0) for the bond-swap pass: Full, Parity and SpinConserve, and XParity
-    over those (the descriptor is then the parent's)."""
+def _swap_subspace(state, what='bond correlations'):
+    """(descriptor's subspace, XParity sector or 0) for the bond-swap and the rotation pass: Full, Parity and
+    SpinConserve, and XParity over those (the descriptor is then the parent's)."""
     from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
     sp = state.subspace
     base, sector = (sp.parent, int(sp.sector)) if type(sp) is XParity else (sp, 0)
     if isinstance(base, Explicit) or not isinstance(base, (Full, Parity, SpinConserve)):
-        raise ValueError('bond correlations need a Full, Parity or SpinConserve subspace, or XParity over one of them, '
-                         'not %r' % (sp,))
+        raise ValueError('%s need a Full, Parity or SpinConserve subspace, or XParity over one of them, not %r'
+                         % (what, sp))
     return sp, sector
 
 
@@ -775,6 +775,79 @@ def bond_correlations(state, bonds, connected=False):
     if connected:
         bb = bb / n - np.outer(b, b) / n ** 2
     return b, bb
+
+
+_CYC_CALL_MAX = 31        # triangles of one call of backend.cyc_moments: two columns each, 63 in all
+_CYC_CHUNK = 15           # longer lists: chunks of this size, one call per pair of chunks on their union
+
+
+def _cyc_gram(state, triangles):
+    """G of backend.cyc_moments for any number of triangles, with the columns 1 + 2 t for the rotation of (a, b, c) and
+    2 + 2 t for that of (a, c, b), its inverse."""
+    from . import backend
+    sp, sector = _swap_subspace(state, 'chirality correlations')
+    sub_c = sp._to_c()
+    n = len(triangles)
+
+    def both_senses(sel):
+        t = triangles[sel]
+        return np.stack([t, t[:, [0, 2, 1]]], axis=1).reshape(-1, 3)
+
+    if n <= _CYC_CALL_MAX:
+        return backend.cyc_moments(state.vec, sub_c, both_senses(np.arange(n)), sector)
+    G = np.zeros((2 * n + 1, 2 * n + 1), dtype=np.complex128)
+    chunks = [np.arange(lo, min(lo + _CYC_CHUNK, n)) for lo in range(0, n, _CYC_CHUNK)]
+    for i in range(len(chunks)):
+        for j in range(i + 1, len(chunks)):
+            # (with more than one chunk every chunk has a partner: the diagonal blocks come with the pairs)
+            sel = np.concatenate([chunks[i], chunks[j]])
+            g = backend.cyc_moments(state.vec, sub_c, both_senses(sel), sector)
+            at = np.concatenate([[0], np.stack([1 + 2 * sel, 2 + 2 * sel], axis=1).reshape(-1)])
+            G[np.ix_(at, at)] = g
+    return G
+
+
+def chirality_correlations(state, triangles, connected=False):
+    """Every scalar chirality and every chirality-chirality correlator of a list of triangles from one pass over
+    ``state`` (one matrix-core kernel, ``backend.cyc_moments``) instead of one ``Operator.expectation`` of a product of
+    two six-term three-body operators per pair of triangles.  ``triangles`` is a list of triples of pairwise distinct
+    sites (a, b, c); a triangle may repeat, triangles may share sites, and the orientation is the caller's
+    (``lattices.kagome_triangles`` gives every triangle of the kagome torus the same sense).  Returns ``(chi, cc)``:
+    ``chi[t]`` = <psi|sigma_a . (sigma_b x sigma_c)|psi>, float64, and ``cc[t, t']`` = <psi|chi_t chi_t'|psi>,
+    complex128 and Hermitian (real for a real state), nothing normalised, as ``expectation`` normalises nothing.
+    ``connected``: ``cc`` is ``cc / n - outer(chi, chi) / n**2`` with n = <psi|psi>, the connected correlator of the
+    normalised state.
+
+    For spin 1/2, sigma_a . (sigma_b x sigma_c) = 2i (C - C^H) with C = P_ab P_bc the rotation of the three spins, and
+    C^H is the rotation of (a, c, b).  With the columns f = 1 + 2 t for (a, b, c) and b = 2 + 2 t for (a, c, b) of the Gram
+    matrix G of the rotated amplitudes: ``chi[t] = -2 (Im G[0, f] - Im G[0, b])`` and ``cc[t, t'] = 4 (G[f, f'] + G[b, b']
+    - G[f, b'] - G[b, f'])``; ``cc[t, t] = 8 G[0, 0] - 8 Re <C_t>`` (chi^2 is 12 on the two doublets of the three spins and
+    0 on the quartet).  A permutation of sites commutes with the global spin flip: states on XParity subspaces are
+    served as they lie.  Full, Parity and SpinConserve states and XParity over those, on one process.  One call of the
+    kernel takes 31 triangles; longer lists are cut into chunks of 15 and every pair of chunks takes one call."""
+    state.assert_initialized()
+    config._initialize()
+    sp, _ = _swap_subspace(state, 'chirality correlations')
+    triangles = np.asarray(triangles, dtype=np.int64)
+    if triangles.size == 0:
+        raise ValueError('chirality correlations of an empty list of triangles')
+    if triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError('triangles must be triples of sites, not an array of shape %r' % (triangles.shape,))
+    if triangles.min() < 0 or triangles.max() >= sp.L:
+        raise ValueError('a triangle has a site outside [0, %d)' % sp.L)
+    if np.any((triangles[:, 0] == triangles[:, 1]) | (triangles[:, 1] == triangles[:, 2])
+              | (triangles[:, 2] == triangles[:, 0])):
+        raise ValueError('the sites of a triangle must be pairwise distinct')
+    G = _cyc_gram(state, triangles)
+    n = G[0, 0].real
+    F, B = G[1::2], G[2::2]             # rows of the two senses
+    chi = -2.0 * (G[0, 1::2].imag - G[0, 2::2].imag)
+    # (the like terms are added to each other first, then the cross terms: cc is then Hermitian to the last bit, as G
+    # is)
+    cc = 4.0 * ((F[:, 1::2] + B[:, 2::2]) - (F[:, 2::2] + B[:, 1::2]))
+    if connected:
+        cc = cc / n - np.outer(chi, chi) / n ** 2
+    return chi, cc
 
 
 def _entropy_of_spectrum(w):

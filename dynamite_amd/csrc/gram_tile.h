@@ -1,9 +1,9 @@
 // The panel scheme of the Gram-matrix sweeps: G = A^H A for an operand matrix A of 16 NB columns whose panels of 2^B
 // rows a workgroup stages in LDS -- the plan of a sweep, the Hermitian rank-4 steps on v_mfma_f64_16x16x4_f64, the sum
 // of the four wavefronts through LDS in a fixed order, the sum of the workgroups' partial tiles and the choice of a
-// kernel instance by subspace type and tile rows.  A sweep adds the panel fill: pm_kernels.hip (sigma+ sigma-) and
-// swap_kernels.hip (bond swaps).  zz_kernels.hip (sigma-z: real symmetric, no panel) takes the wave sum and the choice
-// of the instance.
+// kernel instance by subspace type and tile rows.  A sweep adds the panel fill: pm_kernels.hip (sigma+ sigma-),
+// swap_kernels.hip (bond swaps) and cyc_kernels.hip (three-site rotations, on the bond swaps' plan).  zz_kernels.hip
+// (sigma-z: real symmetric, no panel) takes the wave sum and the choice of the instance.
 //   Re G = Ar^T Ar + Ai^T Ai   (symmetric: lower-triangle tiles, both products into one accumulator)
 //   Q    = Ar^T Ai             (all tiles),   Im G = Q - Q^T
 // partial: [workgroup][Re tile (ti, tj), tj <= ti, at ti (ti + 1) / 2 + tj; then Q tile (ti, tj) at NT + ti NB + tj]
@@ -167,5 +167,18 @@ __device__ __forceinline__ void pm_tile_finalize(const double *__restrict__ part
   out[a * D + b] = make_double2(re, im);
   if (a != b) out[b * D + a] = make_double2(re, -im);
 }
+
+// The plan of the bond-swap sweep (swap_kernels.hip) with the pass named for its messages: ncols - 1 partner columns
+// beside the state's own.
+int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p, const char *what);
+
+// All three-site rotations of a state (cyc_kernels.hip): G = A^H A, A[r, 0] = x(r), A[r, 1 + m] = x(r with the bits of
+// the triple m rotated: bit a <- bit b <- bit c <- bit a) over the rows r of the subspace (xsec = +-1: the
+// representatives of the XParity sector, type / L the parent's); (n + 1) x (n + 1) result.  p: swap_plan(..., ncycles,
+// ...).  x: the whole state (device; Full / Parity as it lies in the swizzled layout swz, SpinConserve in reference
+// order); cycles: 3 ncycles sites (host); nck: pm_binomials(L, k, L + 1) on the device (SpinConserve); partial:
+// p.partial_bytes; out: (ncycles + 1)^2 complex128 (device)
+int launch_cyc_moments(const void *x, int type, int L, int space, int swz, int xsec, int ncycles, const int32_t *cycles,
+                       const GramPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st);
 
 }  // namespace dnm

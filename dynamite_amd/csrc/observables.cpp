@@ -1,10 +1,10 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
-// density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma- and bond-swap moments.  They share the
-// cached scratch of the partial tiles.
+// density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap and three-site rotation
+// (chirality) moments.  They share the cached scratch of the partial tiles.
 #include "gram_tile.h"
 #include "mat.h"
 #include "pm_rank.h"
-#include "swap_rank.h"
+#include "cyc_rank.h"
 
 #include <algorithm>
 #include <cstring>
@@ -349,9 +349,8 @@ int dnm_pm_partner_indices(const dnm_subspace *sub, int64_t n, const int64_t *ro
 }
 
 // ---- bond-swap moments --------------------------------------------------------------------------------------------
-// what the plan, the call and the partner table check alike, before any device call (bonds: null for the plan)
-static int swap_check(const dnm_subspace *sub, int xsec, int nbonds, const int32_t *bonds) {
-  const char *what = "bond-swap moments";
+// what the bond-swap and the rotation pass check alike of the subspace and the sector, before any device call
+static int swap_check_subspace(const dnm_subspace *sub, int xsec, const char *what) {
   DNM_TRY(pm_check(sub, what));
   DNM_CHECK(xsec == 0 || xsec == 1 || xsec == -1, "%s: xparity_sector %d (0, +1 or -1)", what, xsec);
   if (xsec != 0) {
@@ -363,6 +362,13 @@ static int swap_check(const dnm_subspace *sub, int xsec, int nbonds, const int32
       DNM_CHECK(sub->L == 2 * sub->k, "%s: SpinConserve carries the global flip of XParity only when k = L / 2 "
                 "(L=%lld, k=%lld)", what, (long long)sub->L, (long long)sub->k);
   }
+  return 0;
+}
+
+// what the plan, the call and the partner table check alike, before any device call (bonds: null for the plan)
+static int swap_check(const dnm_subspace *sub, int xsec, int nbonds, const int32_t *bonds) {
+  const char *what = "bond-swap moments";
+  DNM_TRY(swap_check_subspace(sub, xsec, what));
   DNM_CHECK(nbonds >= 1 && nbonds <= 63, "%s: %d bonds (1 to 63 in one call)", what, nbonds);
   for (int m = 0; bonds && m < nbonds; ++m) {
     const int a = bonds[2 * m], b = bonds[2 * m + 1];
@@ -429,6 +435,87 @@ int dnm_swap_partner_indices(const dnm_subspace *sub, int xparity_sector, int nb
       }
       idx[i * nbonds + m] = at;
       sign[i * nbonds + m] = (int8_t)(fl ? xparity_sector : 1);
+    }
+  }
+  return 0;
+}
+
+// ---- three-site rotation (scalar chirality) moments ------------------------------------------------------------------
+// what the plan, the call and the partner table check alike, before any device call (cycles: null for the plan)
+static int cyc_check(const dnm_subspace *sub, int xsec, int ncycles, const int32_t *cycles) {
+  const char *what = "chirality moments";
+  DNM_TRY(swap_check_subspace(sub, xsec, what));
+  DNM_CHECK(ncycles >= 1 && ncycles <= 63, "%s: %d cycles (1 to 63 in one call)", what, ncycles);
+  for (int m = 0; cycles && m < ncycles; ++m) {
+    const int a = cycles[3 * m], b = cycles[3 * m + 1], c = cycles[3 * m + 2];
+    DNM_CHECK(a >= 0 && a < sub->L && b >= 0 && b < sub->L && c >= 0 && c < sub->L,
+              "%s: cycle %d = (%d, %d, %d) has a site outside [0, %lld)", what, m, a, b, c, (long long)sub->L);
+    DNM_CHECK(a != b && b != c && c != a, "%s: the sites of cycle %d = (%d, %d, %d) are not pairwise distinct", what, m,
+              a, b, c);
+  }
+  return 0;
+}
+
+int dnm_cyc_moments_plan(const dnm_subspace *sub, int ncycles, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                         size_t *lds_bytes, size_t *scratch_bytes) {
+  DNM_TRY(cyc_check(sub, 0, ncycles, nullptr));
+  GramPlan p;
+  DNM_TRY(swap_plan(sub->type, (int)sub->L, (int)sub->k, ncycles, 0, &p, "chirality"));
+  plan_out(p.nb, p.B, p.nwg, p.lds_bytes, p.partial_bytes, tile_rows, panel_rows_log2, nworkgroups, lds_bytes,
+           scratch_bytes);
+  return 0;
+}
+
+int dnm_cyc_moments(const void *x, const dnm_subspace *sub, int xparity_sector, int ncycles, const int32_t *cycles,
+                    double *out, void *stream) {
+  DNM_CHECK(x && out && cycles, "chirality moments: null argument");
+  DNM_TRY(cyc_check(sub, xparity_sector, ncycles, cycles));
+  const int L = (int)sub->L;
+  GramPlan p;
+  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, ncycles, xparity_sector, &p, "chirality"));
+  return gram_moments(p, L, (size_t)ncycles + 1, "chirality moments", out, stream,
+                      [&](int64_t *table, void *partial, void *G) {
+    return launch_cyc_moments(x, sub->type, L, (int)sub->space, sub->vec_swizzle, xparity_sector, ncycles, cycles, p,
+                              table, partial, G, S(stream));
+  });
+}
+
+int dnm_cyc_partner_indices(const dnm_subspace *sub, int xparity_sector, int ncycles, const int32_t *cycles, int64_t n,
+                            const int64_t *rows, int64_t *idx, int8_t *sign) {
+  DNM_CHECK(cycles, "chirality partner indices: null argument");
+  DNM_TRY(cyc_check(sub, xparity_sector, ncycles, cycles));
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "chirality partner indices: null argument");
+  const int L = (int)sub->L;
+  GramPlan p;
+  DNM_TRY(swap_plan(sub->type, L, (int)sub->k, ncycles, xparity_sector, &p, "chirality"));
+  const bool sc = sub->type == DNM_SPIN_CONSERVE, parity = sub->type == DNM_PARITY;
+  std::vector<int64_t> nck;
+  if (sc) {
+    nck.resize((size_t)(p.K + 1) * (size_t)(L + 1));
+    pm_binomials(L, p.K, L + 1, nck.data());
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t row = rows[i];
+    DNM_CHECK(row >= 0 && row < p.nrows, "chirality partner indices: row %lld of %lld rows", (long long)row,
+              (long long)p.nrows);
+    const uint64_t cfg = sc ? pm_unrank(row, L, p.K, nck.data(), L + 1)
+                         : parity ? ((uint64_t)row << 1) | (uint64_t)(hd_par((uint64_t)row) ^ (int)sub->space)
+                                  : (uint64_t)row;
+    for (int m = 0; m < ncycles; ++m) {
+      const int a = cycles[3 * m], b = cycles[3 * m + 1], c = cycles[3 * m + 2];
+      int fl = 0;
+      int64_t at;
+      if (sc) {
+        at = cyc_sc_partner(cfg, row, a, b, c, L, p.dim, xparity_sector, nck.data(), L + 1, &fl);
+      } else {
+        int pp, qq;
+        const int d = cyc_changed(cfg, a, b, c, &pp, &qq);
+        fl = cyc_flipped(d, a, b, c, L, xparity_sector);
+        at = cyc_xor_partner(row, d, fl, cyc_site_mask(parity, a), cyc_site_mask(parity, b), cyc_site_mask(parity, c),
+                             cyc_all_mask(parity, L));
+      }
+      idx[i * ncycles + m] = at;
+      sign[i * ncycles + m] = (int8_t)(fl ? xparity_sector : 1);
     }
   }
   return 0;

@@ -31,8 +31,9 @@ constexpr int SWAP_ROWS_PER_WG_LOG2 = 9;        // workgroups = ceil(rows / 2^9)
 
 static_assert(SWAP_B_MAX <= SWAP_ROWS_PER_WG_LOG2, "a workgroup has at least one panel");
 
-// rows: the subspace's own (the representatives of an XParity sector), with the binomials of sector K = k
-int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p) {
+// rows: the subspace's own (the representatives of an XParity sector), with the binomials of sector K = k; `what`: the
+// pass, for the messages (gram_tile.h: the rotation pass plans through this too)
+int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p, const char *what) {
   GramPlan q{};
   q.K = type == DNM_SPIN_CONSERVE ? k : 0;
   size_t table_bytes = 0;
@@ -43,7 +44,7 @@ int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p) {
     table_bytes = t.size() * sizeof(int64_t);
   } else {
     if (L - (type == DNM_PARITY) > 62) {
-      set_error("bond-swap moments: 2^%d rows", L - (type == DNM_PARITY));
+      set_error("%s moments: 2^%d rows", what, L - (type == DNM_PARITY));
       return 1;
     }
     q.dim = (int64_t)1 << (L - (type == DNM_PARITY));
@@ -51,11 +52,15 @@ int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p) {
   const int64_t nrows = xsec ? q.dim / 2 : q.dim;
   const int64_t nwg = (nrows + ((int64_t)1 << SWAP_ROWS_PER_WG_LOG2) - 1) >> SWAP_ROWS_PER_WG_LOG2;
   if (!gram_plan(nbonds + 1, nrows, table_bytes, SWAP_B_MAX, SWAP_B_MAX_WIDE, SWAP_B_MIN, 0, nwg, &q)) {
-    set_error("internal: bond-swap panel of %zu bytes", q.lds_bytes);
+    set_error("internal: %s panel of %zu bytes", what, q.lds_bytes);
     return 1;
   }
   *p = q;
   return 0;
+}
+
+int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p) {
+  return swap_plan(type, L, k, nbonds, xsec, p, "bond-swap");
 }
 
 struct SwapArgs {

@@ -28,9 +28,9 @@ def _is_site(p):
     return p[0] % 2 == 0 or p[1] % 2 == 1
 
 
-def kagome(cluster):
-    """(number of sites, sorted list of edges (i, j), i < j) of a kagome torus; ``cluster`` is a name of
-    ``KAGOME_CLUSTERS`` or a pair of spanning vectors."""
+def _kagome_walk(cluster):
+    """(points in the order of their numbering, point -> number, the reduction into the torus, set of edges) of a
+    kagome torus."""
     (a0, a1), (b0, b1) = KAGOME_CLUSTERS[cluster] if isinstance(cluster, str) else cluster
     A, B = (2 * a0, 2 * a1), (2 * b0, 2 * b1)
     det = A[0] * B[1] - A[1] * B[0]
@@ -64,7 +64,35 @@ def kagome(cluster):
             if at < j:
                 edges.add((at, j))
         at += 1
+    return order, index, wrap, edges
+
+
+def kagome(cluster):
+    """(number of sites, sorted list of edges (i, j), i < j) of a kagome torus; ``cluster`` is a name of
+    ``KAGOME_CLUSTERS`` or a pair of spanning vectors."""
+    order, _, _, edges = _kagome_walk(cluster)
     return len(order), sorted(edges)
+
+
+def kagome_triangles(cluster):
+    """The 2 N / 3 elementary triangles of the torus ``kagome(cluster)`` builds, with its site numbering: a sorted list
+    of (a, b, c) with a the smallest site, every triangle in the same sense -- (p, p + n_{k+1}, p + n_k) for consecutive
+    entries n_k, n_{k+1} of ``_NEIGHBOURS`` with all three points sites, which is anticlockwise in the usual embedding
+    of the skew coordinates ((1, 0) along x, (0, 1) at 60 degrees).  These are the geometric triangles, each edge in
+    exactly one of them, not the 3-cycles of the edge graph, of which small tori have more.  With this list
+    ``State.chirality_correlations`` gives the scalar chiralities of one orientation of the plane."""
+    order, index, wrap, _ = _kagome_walk(cluster)
+    found = set()
+    for at, (x, y) in enumerate(order):
+        for k in range(len(_NEIGHBOURS)):
+            (dx0, dy0), (dx1, dy1) = _NEIGHBOURS[k], _NEIGHBOURS[(k + 1) % len(_NEIGHBOURS)]
+            q1, q0 = wrap((x + dx1, y + dy1)), wrap((x + dx0, y + dy0))
+            if not (_is_site(q1) and _is_site(q0)):
+                continue
+            t = (at, index[q1], index[q0])
+            first = t.index(min(t))
+            found.add(t[first:] + t[:first])
+    return sorted(found)
 
 
 def chain(L, periodic=False):

@@ -280,6 +280,12 @@ class State:
         from . import computations
         return computations.bond_correlations(self, bonds, connected=connected)
 
+    def chirality_correlations(self, triangles, connected=False):
+        """``(chi, cc)``: every <sigma_a . (sigma_b x sigma_c)> and every <chi_t chi_t'> of the triangles in one pass
+        -> computations.chirality_correlations."""
+        from . import computations
+        return computations.chirality_correlations(self, triangles, connected=connected)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

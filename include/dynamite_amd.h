@@ -274,6 +274,44 @@ int dnm_swap_moments(const void *x, const dnm_subspace *sub, int xparity_sector,
                      double *out, void *stream);
 int dnm_swap_partner_indices(const dnm_subspace *sub, int xparity_sector, int nbonds, const int32_t *bonds, int64_t n,
                              const int64_t *rows, int64_t *idx, int8_t *sign);
+/* Every scalar-chirality correlator of a list of triangles in one pass over the state (no counterpart in the reference,
+ * whose users call Operator.expectation once per pair of triangles).  For spin 1/2, sigma_a . (sigma_b x sigma_c) =
+ * 2i (C - C^H) with C = P_ab P_bc (P_bc acts first) the rotation of the three spins.  For ncycles oriented triples
+ * (a_m, b_m, c_m) = (cycles[3 m], cycles[3 m + 1], cycles[3 m + 2]) of pairwise distinct sites -- a triple may repeat,
+ * triples may share sites -- and the operand matrix over the rows r of the subspace
+ *   A[r][0] = x(r),   A[r][1 + m] = x(r'),  bit a of r' = bit b of r, bit b of r' = bit c of r, bit c of r' = bit a of r,
+ *   G = A^H A      ((ncycles + 1) x (ncycles + 1) complex128, row-major, Hermitian):
+ * column 1 + m is C_m x, G[0][0] = <x|x>, G[0][1 + m] = <C_m>, G[1 + m][1 + m'] = <C_m^H C_m'>.  The opposite rotation of
+ * (a, b, c) is the rotation of (a, c, b): one triple is one column and the caller lists both senses.  Sums are raw
+ * (nothing is normalised).  G equals its conjugate transpose to the last bit, its diagonal is real, and two calls return
+ * the same bits on any device (no atomics; the number of workgroups follows from the number of rows alone).
+ * x (device) is the WHOLE state on one device.  Layouts: Full / Parity in index order or XOR-swizzled, read as it lies;
+ * SpinConserve in reference order.  xparity_sector = +-1: x holds the dim / 2 amplitudes of the representatives of that
+ * XParity sector and sub is the parent's descriptor (the convention of dnm_swap_moments); a permutation of sites
+ * commutes with the global flip, so the sum over the representatives -- with the partner of a row taken as the sector's
+ * sign times the amplitude of its complement where the rotation sets bit L - 1 -- is the expectation value in the sector.
+ * Refused, each before any device call: null pointers, Explicit subspaces, an unknown subspace type, L outside [1, 64],
+ * ncycles outside [1, 63], a site outside [0, L) or two equal sites in a triple, a non-null site_perm, the SpinConserve
+ * internal layout (the caller converts: dnm_vec_layout_copy), a Full / Parity swizzle shift outside {0} and [5, 24],
+ * xparity_sector other than 0, +1, -1, and an XParity parent that cannot carry the flip (Parity with odd L, SpinConserve
+ * with L != 2 k).
+ * out: HOST, (ncycles + 1)^2 * 2 doubles (re, im); the call synchronises the stream like dnm_vec_dot.  Scratch comes
+ * from the library's workspace (dnm_release_workspace).
+ * dnm_cyc_moments_plan (host only, no device needed): the plan of dnm_swap_moments_plan for the same number of columns
+ * -- tile_rows = ceil((ncycles + 1) / 16) rows of 16 x 16 tiles (NB), the panel of 2^panel_rows_log2 rows of A a
+ * workgroup stages in LDS, the workgroups of the sweep -- ceil(rows / 512), at most 1024 -- the bytes of LDS of a launch
+ * (at most 152 KB) and the bytes of the partial tiles, nworkgroups * (NB (NB + 1) / 2 + NB^2) * 256 * 8; any output may
+ * be null.
+ * dnm_cyc_partner_indices (host only): for each of the n rows (indices into x) and each triple, idx[row * ncycles + m] =
+ * the reference-order index into x of the amplitude A[row][1 + m] is taken from and sign[row * ncycles + m] its factor:
+ * +1, or the sector where the complement's amplitude was taken.  The arithmetic is the kernel's (csrc/cyc_rank.h,
+ * csrc/swap_rank.h). */
+int dnm_cyc_moments_plan(const dnm_subspace *sub, int ncycles, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                         size_t *lds_bytes, size_t *scratch_bytes);
+int dnm_cyc_moments(const void *x, const dnm_subspace *sub, int xparity_sector, int ncycles, const int32_t *cycles,
+                    double *out, void *stream);
+int dnm_cyc_partner_indices(const dnm_subspace *sub, int xparity_sector, int ncycles, const int32_t *cycles, int64_t n,
+                            const int64_t *rows, int64_t *idx, int8_t *sign);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
