@@ -629,6 +629,7 @@ int dnm_mat_create(int64_t nmasks, const int64_t *masks, const int64_t *mask_off
   DNM_CHECK(A->left.host.L == A->right.host.L, "left and right subspaces have different L");
   A->M = A->left.host.dim;
   A->N = A->right.host.dim;
+  A->one_subspace = same_subspace(A->left, A->right);
   if (A->xparity) {
     // The operator has been rewritten by XParity.reduce_msc (subspaces.py:632-674) and the basis is
     // the first half of the parent's: halving the dimensions is all the backend does
@@ -838,11 +839,15 @@ int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream) {
   DNM_CHECK(!A->real_packed || (A->use_sc3 && A->sc3->diag_mode == 1),
             "this real-packed operator evaluates its diagonal on the fly: nothing to precompute");
   // only when the first mask is the identity (bpetsc_template_1.c:177-180) and
-  // left == right (operators.py:627-629; the caller guarantees it)
+  // left == right (operators.py:627-629)
   if (A->masks.empty() || A->masks[0] != 0) return 0;
   DNM_CHECK(A->nranks == 1 || A->route != Route::Tiled,
             "precomputed diagonal is not used by the partitioned tiled multiply");
   DNM_CHECK(A->M == A->N, "precompute_diagonal needs a square matrix");
+  // (equal dimensions are not enough: the row kernels add diag[row] x[row], and between two different subspaces the
+  // identity mask pairs row i with the column of the SAME state, if the right subspace holds it at all)
+  DNM_CHECK(A->one_subspace,
+            "precompute_diagonal needs the same subspace on both sides (this handle projects between two)");
   if (A->use_sc3) {
     // computed row by row in reference order, kept in the vectors' layout: the share needs a reference side (every share
     // of block order 0, whole vectors of the others) -- asked before anything is launched

@@ -23,6 +23,20 @@ struct SubOwned {
 };
 // the checked view of a caller's descriptor: its tables stay the caller's (mat.cpp)
 int view_from_c(const dnm_subspace *s, SubView *v);
+// Do two descriptors name the same subspace -- the same states at the same indices?  (Equal dimensions do not say so:
+// SpinConserve(10, 4) and SpinConserve(10, 6), two Explicit lists of one length, the two Parity sectors.)  The vector
+// layout is not part of the question.  Explicit: a compare of the two state lists -- dnm_mat_create asks once and keeps
+// the answer (dnm_mat::one_subspace); nothing on the path of a multiply calls this.
+inline bool same_subspace(const SubOwned &a, const SubOwned &b) {
+  const SubView &x = a.host, &y = b.host;
+  if (x.type != y.type || x.L != y.L) return false;
+  switch (x.type) {
+    case DNM_PARITY: return x.space == y.space;
+    case DNM_SPIN_CONSERVE: return x.k == y.k;
+    case DNM_EXPLICIT: return a.smap == b.smap;
+  }
+  return true;
+}
 
 // What one launch of the tiled kernel reads, as passes.cpp builds it on the host
 struct PassRecords {
@@ -86,6 +100,7 @@ struct dnm_mat {
   int64_t M = 0, N = 0, m_local = 0, n_local = 0;
   int64_t row0 = 0;               // first row / column this rank owns
   bool sc_pair = false;           // SpinConserve(L,k) on both sides: incremental-rank kernel
+  bool one_subspace = false;      // left and right name the same subspace (same_subspace, asked once by dnm_mat_create)
   // SpinConserve(L,k) on both sides with vectors in the internal layout (sc3.h): m_local / n_local then count the
   // padding too (they are what the vector kernels sweep), rows_local the rows
   bool use_sc3 = false;

@@ -229,6 +229,15 @@ int dnm_mat_mult_lanczos(dnm_mat *A, const void *x, void *y, const void *z, doub
   DNM_CHECK(A && x && y && dot, "null argument");
   DNM_CHECK(A->remote_passes.empty(), "operator couples different ranks: no fused Lanczos step");
   DNM_CHECK(z != y && x != y, "y must not alias x or z");
+  // <x, y> pairs element i of x with element i of y: on a handle between two subspaces that is no inner product, and
+  // with M > N the sweep of the sums (a route that does not fuse them) would read past the end of x; the sweep pairs
+  // by position in memory, so one subspace in two vector layouts is no inner product either (dnm_mat_create turns a
+  // Full / Parity pair of two layouts away already: this is the statement of what the sums need, at their entry)
+  DNM_CHECK(A->one_subspace,
+            "the sums of a Lanczos step need the same subspace on both sides (this handle projects between two)");
+  DNM_CHECK(A->left.host.swz == A->right.host.swz,
+            "the sums of a Lanczos step need x and y in one vector layout (left vec_swizzle %d, right %d)",
+            A->left.host.swz, A->right.host.swz);
   return mult_fused(A, x, y, RowFuse{z, b}, dot, stream);
 }
 

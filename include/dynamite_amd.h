@@ -318,7 +318,9 @@ int dnm_mat_destroy(dnm_mat *A);
 int dnm_mat_sizes(const dnm_mat *A, int64_t *M, int64_t *N, int64_t *m_local, int64_t *n_local);
 /* PrecomputeDiagonal(A) (bpetsc.pyx:141-147, bcuda_template_1.cu:4-66).  The
  * tiled Full/Parity kernels evaluate the diagonal on the fly and ignore the
- * cache; the generic kernel uses it exactly as the reference does. */
+ * cache; the generic kernel uses it exactly as the reference does.  An error on a
+ * handle whose left and right descriptors name different subspaces, equal dimensions or
+ * not (SpinConserve(L, k) / SpinConserve(L, L - k), two Explicit lists of one length). */
 int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream);
 /* copies the cached diagonal (double[m_local]) to the host; error if absent */
 int dnm_mat_get_diagonal(dnm_mat *A, double *diag_host, void *stream);
@@ -405,7 +407,8 @@ int dnm_mat_exchange_plan(const dnm_mat *A, int *nsend, dnm_xfer *sends /* may b
 int dnm_mat_mult_dot(dnm_mat *A, const void *x, void *y, double *dot /* [2], host */, void *stream);
 /* One Lanczos step's multiply: y = A x - b z (z may be NULL), dot[0] + i dot[1] = <x, y> and
  * dot[2] = |y|^2 (beta^2 = |y|^2 - |alpha|^2 without another sweep); the beta term starts the
- * accumulators of the first pass, the sums close the last. */
+ * accumulators of the first pass, the sums close the last.  The sums pair x_i with y_i:
+ * an error (here and in dnm_mat_mult_dot) on a handle between two different subspaces. */
 int dnm_mat_mult_lanczos(dnm_mat *A, const void *x, void *y, const void *z, double b,
                          double *dot /* [3], host */, void *stream);
 /* y = A x - b z (three-term recurrences without inner products, e.g. Chebyshev).  Single rank only. */
