@@ -1980,6 +1980,65 @@ def cyc_moments(vec, subspace, cycles, xparity_sector=0):
     return out
 
 
+def _pauli_cols_c(cols):
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, 2)
+    return cols, cols.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def pauli_moments_plan(sub_c, ncols):
+    """``dnm_pauli_moments_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
+    launch, bytes of the partial tiles) of the Pauli sweep with ``ncols`` columns over a state of the subspace -- the
+    bond-swap plan for the same number of columns."""
+    tr, pb, nw, lb, sb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_pauli_moments_plan(C.byref(sub_c), int(ncols), C.byref(tr), C.byref(pb), C.byref(nw),
+                                                 C.byref(lb), C.byref(sb)))
+    return tr.value, pb.value, nw.value, int(lb.value), int(sb.value)
+
+
+def pauli_partner_indices(sub_c, cols, rows):
+    """``dnm_pauli_partner_indices`` (host only): ``(idx, sign)``, int64 and int8 arrays (len(rows), len(cols)) -- for
+    the row of reference-order index ``rows[n]`` of the vector and column c = (site, kind), the reference-order index
+    into the vector of the amplitude the column takes there (the row's own, or that of the row with the site flipped)
+    and its factor +-1."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    cols, cp = _pauli_cols_c(cols)
+    idx = np.empty((rows.size, cols.shape[0]), dtype=np.int64)
+    sign = np.empty((rows.size, cols.shape[0]), dtype=np.int8)
+    _lib.check(_lib.lib().dnm_pauli_partner_indices(C.byref(sub_c), cols.shape[0], cp, rows.size, _lib.p64(rows),
+                                                    _lib.p64(idx), sign.ctypes.data_as(C.POINTER(C.c_int8))))
+    return idx, sign
+
+
+def pauli_moments(vec, subspace, cols):
+    """The raw single-site Pauli moments of the state in ``vec`` in one pass: numpy array G of shape (n + 1, n + 1),
+    complex128, for the n <= 63 columns ``cols`` = [(site_0, kind_0), ...] with kind 1 a flip (sigma-x), 2 a flip and a
+    sign (sigma-y up to its phase -i) and 3 a sign (sigma-z): G = A^H A with A[q, 0] = psi(q) and A[q, 1 + c] = +-psi(q
+    with the site flipped, or q itself), so that column 1 + c is sigmax psi, i sigmay psi or sigmaz psi and G holds
+    <psi|psi>, every <sigma_c> and every <sigma_c sigma_c'> up to those phases (raw sums, nothing normalised; G is
+    Hermitian to the last bit).  ``subspace`` is the descriptor of the Full or Parity subspace of the vector; on Parity
+    the entries between a flipping and a non-flipping column, which vanish by symmetry, are exact zeros.  Swizzled
+    vectors are read as they lie.  SpinConserve and Explicit descriptors are refused.  The partners of a rank's rows
+    lie on other ranks: on more than one rank this raises ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('Pauli moments of a partitioned state: the partner amplitudes of a rank\'s rows lie '
+                                  'on other ranks')
+    cols, cp = _pauli_cols_c(cols)
+    n = cols.shape[0]
+    sub_c = subspace['data']
+    # (refused descriptors never get as far as a copy of the vector)
+    _lib.check(_lib.lib().dnm_pauli_moments_plan(C.byref(sub_c), n, None, None, None, None, None))
+    x, sub_c = _reference_order(vec, sub_c)
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(sub_c), C.byref(full)))
+    if x.numel() != full.value:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), full.value))
+    out = np.empty((n + 1, n + 1), dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_pauli_moments(C.c_void_p(x.data_ptr()), C.byref(sub_c), n, cp,
+                                            out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return out
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

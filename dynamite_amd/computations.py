@@ -850,6 +850,207 @@ def chirality_correlations(state, triangles, connected=False):
     return chi, cc
 
 
+_PAULI_CALL_MAX = 63      # columns of one call of backend.pauli_moments
+_PAULI_CHUNK = 31         # longer lists: chunks of at most this size, one call per pair of chunks on their union
+_PAULI_KINDS = (1, 2, 3)  # the kinds of backend.pauli_moments for the axis index 0, 1, 2 = x, y, z
+
+
+def _pauli_subspace(state, what='Pauli correlations'):
+    from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
+    sp = state.subspace
+    if type(sp) is XParity:
+        raise ValueError('%s of an XParity state: sigmaz_i does not commute with the global spin flip, so the sum over '
+                         'the representatives is not the expectation value (expand the state first)' % what)
+    if isinstance(sp, Explicit) or not isinstance(sp, (Full, Parity, SpinConserve)):
+        raise ValueError('%s need a Full, Parity or SpinConserve subspace, not %r' % (what, sp))
+    return sp
+
+
+def _pauli_chunks(cols):
+    """The columns ``cols`` (site, kind) cut into chunks of at most _PAULI_CHUNK: the flipping columns in the order of
+    their sites, so that the sigma-x and sigma-y columns of a site (and repeats) share a chunk, a call and its loads
+    wherever the site has no more columns than a chunk holds; then the columns that only sign."""
+    flips = cols[:, 1] != 3
+    order = np.concatenate([np.flatnonzero(flips)[np.argsort(cols[flips, 0], kind='stable')], np.flatnonzero(~flips)])
+    groups, at = [], 0
+    while at < len(order):
+        c = order[at]
+        end = at + 1
+        while flips[c] and end < len(order) and flips[order[end]] and cols[order[end], 0] == cols[c, 0]:
+            end += 1
+        groups += [order[lo:min(lo + _PAULI_CHUNK, end)] for lo in range(at, end, _PAULI_CHUNK)]
+        at = end
+    chunks = [[]]
+    for g in groups:
+        if len(chunks[-1]) + len(g) > _PAULI_CHUNK:
+            chunks.append([])
+        chunks[-1].extend(g)
+    return [np.array(c, dtype=np.int64) for c in chunks]
+
+
+def _pauli_gram(state, cols):
+    """G of backend.pauli_moments for any number of columns (site, kind): G[0, 0], G[0, 1 + c] and G[1 + c, 1 + c'] in
+    the order of ``cols``, without the phase of the sigma-y columns."""
+    from . import backend
+    sub_c = state.subspace._to_c()
+    cols = np.asarray(cols, dtype=np.int64).reshape(-1, 2)
+    n = len(cols)
+    if n <= _PAULI_CALL_MAX:
+        return backend.pauli_moments(state.vec, sub_c, cols)
+    G = np.zeros((n + 1, n + 1), dtype=np.complex128)
+    chunks = _pauli_chunks(cols)
+    for i in range(len(chunks)):
+        for j in range(i + 1, len(chunks)):
+            # (with more than one chunk every chunk has a partner: the diagonal blocks come with the pairs)
+            sel = np.concatenate([chunks[i], chunks[j]])
+            g = backend.pauli_moments(state.vec, sub_c, cols[sel])
+            at = np.concatenate([[0], 1 + sel])
+            G[np.ix_(at, at)] = g
+    return G
+
+
+def _pauli_sites(state, sites):
+    L = state.subspace.L
+    sites = np.arange(L, dtype=np.int64) if sites is None else np.asarray(sites, dtype=np.int64)
+    if sites.size == 0:
+        raise ValueError('Pauli correlations of an empty list of sites')
+    if sites.ndim != 1:
+        raise ValueError('sites must be a list of sites, not an array of shape %r' % (sites.shape,))
+    if sites.min() < 0 or sites.max() >= L:
+        raise ValueError('a site outside [0, %d)' % L)
+    return sites
+
+
+def _pauli_from_u1(state, sites):
+    """(one, two) of a SpinConserve state from the sigma-z and the sigma+ sigma- pass: the flipping operators come in
+    the pairs that conserve the magnetisation only."""
+    mz, zz = sigmaz_correlations(state)
+    pm = sigma_pm_correlations(state)
+    n = len(sites)
+    at = np.ix_(sites, sites)
+    one = np.zeros((3, n))
+    one[2] = mz[sites]
+    two = np.zeros((3, n, 3, n), dtype=np.complex128)
+    half = 0.5 * pm[at]
+    two[0, :, 0, :] = half.real
+    two[1, :, 1, :] = half.real
+    two[1, :, 0, :] = half.imag
+    two[0, :, 1, :] = -half.imag
+    two[2, :, 2, :] = zz[at]
+    # the same site twice: sigma^a sigma^a = 1 and sigmax sigmay = i sigmaz (sigmay sigmaz = i sigmax and sigmaz sigmax
+    # = i sigmay have no expectation value in the sector)
+    norm2 = zz[0, 0]
+    same = sites[:, None] == sites[None, :]
+    for a in range(2):
+        two[a, :, a, :][same] = norm2
+    i_mz = 1j * np.broadcast_to(mz[sites][:, None], (n, n))
+    two[0, :, 1, :][same] = i_mz[same]
+    two[1, :, 0, :][same] = -i_mz[same]
+    return one, two
+
+
+def pauli_correlations(state, sites=None):
+    """Every single-site Pauli expectation value and every two-site Pauli correlator of ``state`` on the spins ``sites``
+    (default: all of them; a site may repeat) from one pass over it (one matrix-core kernel, ``backend.pauli_moments``)
+    instead of one ``Operator.expectation`` per correlator, each a multiply and a temporary vector -- for the states
+    without a U(1) symmetry, where <sigmax sigmax> != <sigmay sigmay> and <sigmax sigmaz> and <sigmax> need not vanish.
+    Returns ``(one, two)`` with the axis index a = 0, 1, 2 for x, y, z: ``one[a, i]`` = <psi|sigma^a_{s_i}|psi>, float64
+    of shape (3, n), and ``two[a, i, b, j]`` = <psi|sigma^a_{s_i} sigma^b_{s_j}|psi>, complex128 of shape (3, n, 3, n),
+    nothing normalised, as ``expectation`` normalises nothing.  Entries at the same site follow from the definition:
+    ``two[0, i, 1, i]`` = i <sigmaz_i> and ``two[a, i, a, i]`` = <psi|psi>.  Reshaped to 3n x 3n, ``two`` is Hermitian to
+    the last bit.
+
+    sigmax_j psi, i sigmay_j psi and sigmaz_j psi are each one partner amplitude times a sign; ``two`` is the Gram
+    matrix of those columns with the phase -i of sigma-y applied afterwards (the row times the conjugate phase, the
+    column times the phase: both exact).  One call of the kernel takes 63 columns; longer lists (all sites from L = 22
+    on) are cut into chunks of at most 31 and every pair of chunks takes one call.  Full and Parity states on one
+    process; on Parity the entries with an odd number of flips are exact zeros.  SpinConserve states are assembled from
+    ``sigmaz_correlations`` and ``sigma_pm_correlations`` (XX = YY = Re pm / 2, YX = -XY = Im pm / 2, nothing else with
+    a flip survives).  XParity states are refused: sigmaz_i does not commute with the global flip."""
+    from .subspaces import SpinConserve
+    state.assert_initialized()
+    config._initialize()
+    sp = _pauli_subspace(state)
+    sites = _pauli_sites(state, sites)
+    if isinstance(sp, SpinConserve):
+        return _pauli_from_u1(state, sites)
+    n = len(sites)
+    # column 3 i + a of the list: kind a + 1 at site s_i
+    cols = np.stack([np.repeat(sites, 3), np.tile(_PAULI_KINDS, n)], axis=1)
+    G = _pauli_gram(state, cols)
+    phase = np.tile(np.array([1.0, -1j, 1.0]), n)
+    one = (G[0, 1:] * phase).real.reshape(n, 3).T.copy()
+    two = (np.conj(phase)[:, None] * G[1:, 1:]) * phase[None, :]
+    return one, two.reshape(n, 3, n, 3).transpose(1, 0, 3, 2).copy()
+
+
+_PAULI_MATRICES = np.array([[[1, 0], [0, 1]], [[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]],
+                           dtype=np.complex128)       # 1, x, y, z on (clear bit, set bit)
+
+
+def _pair_density_matrices(one, two, norm2, at):
+    """rho_ij for the pairs ``at`` of positions in the site list of (one, two): the index of the basis is bit_i + 2 bit_j,
+    as reduced_density_matrix(state, [i, j]) has it."""
+    out = np.empty((len(at), 4, 4), dtype=np.complex128)
+    for n, (i, j) in enumerate(at):
+        # c[a, b] = <sigma^a_i sigma^b_j> with a, b = 0 for the identity
+        c = np.empty((4, 4), dtype=np.complex128)
+        c[0, 0] = norm2
+        c[1:, 0] = one[:, i]
+        c[0, 1:] = one[:, j]
+        c[1:, 1:] = two[:, i, :, j]
+        out[n] = np.einsum('ab,bkl,amn->kmln', c, _PAULI_MATRICES, _PAULI_MATRICES).reshape(4, 4) / (4.0 * norm2)
+    return out
+
+
+def two_site_density_matrices(state, pairs=None):
+    """The reduced density matrices of pairs of spins from the Pauli correlators of one pass over ``state``
+    (``pauli_correlations``) instead of one ``reduced_density_matrix`` per pair: array of shape (len(pairs), 4, 4),
+    complex128, ``rho_ij = 1/4 sum_{a, b in 1, x, y, z} <sigma^a_i sigma^b_j> sigma^a (x) sigma^b / <psi|psi>`` in the
+    basis order of ``reduced_density_matrix(state, [i, j])``.  ``pairs`` are (i, j) with i < j; default: all of them."""
+    state.assert_initialized()
+    _pauli_subspace(state, 'two-site density matrices')
+    L = state.subspace.L
+    if pairs is None:
+        pairs = [(i, j) for i in range(L) for j in range(i + 1, L)]
+    pairs = np.asarray(pairs, dtype=np.int64)
+    if pairs.size == 0:
+        raise ValueError('two-site density matrices of an empty list of pairs')
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError('pairs must be pairs of sites, not an array of shape %r' % (pairs.shape,))
+    if pairs.min() < 0 or pairs.max() >= L:
+        raise ValueError('a pair has a site outside [0, %d)' % L)
+    if np.any(pairs[:, 0] >= pairs[:, 1]):
+        raise ValueError('a pair (i, j) must have i < j')
+    sites, at = np.unique(pairs, return_inverse=True)
+    one, two = pauli_correlations(state, sites)
+    return _pair_density_matrices(one, two, two[0, 0, 0, 0].real, at.reshape(-1, 2))
+
+
+def mutual_information(state, sites=None):
+    """The mutual information ``I_ij = S_i + S_j - S_ij`` (natural logarithm) of every pair of the spins ``sites``
+    (default: all of them) from the Pauli correlators of one pass over ``state``: (n, n) float64, symmetric with a zero
+    diagonal.  The spectra of the one- and two-site density matrices come from ``numpy.linalg.eigvalsh``, clipped at 0."""
+    state.assert_initialized()
+    _pauli_subspace(state, 'mutual information')
+    sites = _pauli_sites(state, sites)
+    one, two = pauli_correlations(state, sites)
+    n = len(sites)
+    norm2 = two[0, 0, 0, 0].real
+
+    def entropy(rho):
+        return _entropy_of_spectrum(np.clip(np.linalg.eigvalsh(rho), 0.0, None))
+
+    single = [entropy(0.5 * (_PAULI_MATRICES[0] + np.einsum('a,akl->kl', one[:, i] / norm2, _PAULI_MATRICES[1:])))
+              for i in range(n)]
+    out = np.zeros((n, n))
+    at = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    if at:
+        for (i, j), rho in zip(at, _pair_density_matrices(one, two, norm2, at)):
+            out[i, j] = out[j, i] = single[i] + single[j] - entropy(rho)
+    return out
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

@@ -2,7 +2,8 @@
 // rows a workgroup stages in LDS -- the plan of a sweep, the Hermitian rank-4 steps on v_mfma_f64_16x16x4_f64, the sum
 // of the four wavefronts through LDS in a fixed order, the sum of the workgroups' partial tiles and the choice of a
 // kernel instance by subspace type and tile rows.  A sweep adds the panel fill: pm_kernels.hip (sigma+ sigma-),
-// swap_kernels.hip (bond swaps) and cyc_kernels.hip (three-site rotations, on the bond swaps' plan).  zz_kernels.hip
+// swap_kernels.hip (bond swaps), cyc_kernels.hip (three-site rotations, on the bond swaps' plan) and pauli_kernels.hip
+// (single-site Paulis, on that plan too).  zz_kernels.hip
 // (sigma-z: real symmetric, no panel) takes the wave sum and the choice of the instance.
 //   Re G = Ar^T Ar + Ai^T Ai   (symmetric: lower-triangle tiles, both products into one accumulator)
 //   Q    = Ar^T Ai             (all tiles),   Im G = Q - Q^T
@@ -180,5 +181,13 @@ int swap_plan(int type, int L, int k, int nbonds, int xsec, GramPlan *p, const c
 // p.partial_bytes; out: (ncycles + 1)^2 complex128 (device)
 int launch_cyc_moments(const void *x, int type, int L, int space, int swz, int xsec, int ncycles, const int32_t *cycles,
                        const GramPlan &p, const int64_t *nck, void *partial, void *out, hipStream_t st);
+
+// All single-site Pauli columns of a state (pauli_kernels.hip): G = A^H A, A[q, 0] = x(q), A[q, 1 + c] = +-x(q ^ m_c) for
+// the columns c = (site, kind: 1 flip, 2 flip and sign, 3 sign) of pauli_cols.h over the rows q of a Full or Parity
+// vector; (ncols + 1) x (ncols + 1) result, on Parity with the entries between a flipping and a non-flipping column
+// still to be zeroed by the caller.  p: swap_plan(type, L, 0, ncols, 0, ...).  x: the whole state (device, as it lies in
+// the swizzled layout swz); cols: 2 ncols ints (host); partial: p.partial_bytes; out: (ncols + 1)^2 complex128 (device)
+int launch_pauli_moments(const void *x, int type, int L, int space, int swz, int ncols, const int32_t *cols,
+                         const GramPlan &p, void *partial, void *out, hipStream_t st);
 
 }  // namespace dnm

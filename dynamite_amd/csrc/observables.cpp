@@ -1,10 +1,11 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
-// density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap and three-site rotation
-// (chirality) moments.  They share the cached scratch of the partial tiles.
+// density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap, three-site rotation
+// (chirality) and two-spin Pauli moments.  They share the cached scratch of the partial tiles.
 #include "gram_tile.h"
 #include "mat.h"
 #include "pm_rank.h"
 #include "cyc_rank.h"
+#include "pauli_cols.h"
 
 #include <algorithm>
 #include <cstring>
@@ -516,6 +517,91 @@ int dnm_cyc_partner_indices(const dnm_subspace *sub, int xparity_sector, int ncy
       }
       idx[i * ncycles + m] = at;
       sign[i * ncycles + m] = (int8_t)(fl ? xparity_sector : 1);
+    }
+  }
+  return 0;
+}
+
+// ---- two-spin Pauli moments ---------------------------------------------------------------------------------------
+// what the plan, the call and the partner table check alike, before any device call (cols: null for the plan)
+static int pauli_check(const dnm_subspace *sub, int ncols, const int32_t *cols) {
+  const char *what = "Pauli moments";
+  DNM_CHECK(sub, "%s: null subspace descriptor", what);
+  DNM_CHECK(sub->type != DNM_EXPLICIT, "%s: Explicit subspaces are not supported (a flipped row may lie outside the "
+            "subspace)", what);
+  DNM_CHECK(sub->type != DNM_SPIN_CONSERVE, "%s: SpinConserve subspaces are not supported: a flip leaves the sector "
+            "(dnm_zz_moments and dnm_pm_moments hold every correlator that does not vanish there)", what);
+  DNM_CHECK(sub->type == DNM_FULL || sub->type == DNM_PARITY, "%s: unknown subspace type %d", what, sub->type);
+  DNM_CHECK(sub->L >= 1 && sub->L <= 64, "%s: L=%lld out of range (at most 64 spins)", what, (long long)sub->L);
+  const int bits = (int)sub->L - (sub->type == DNM_PARITY);
+  DNM_CHECK(bits <= 62, "%s: %d index bits (2^%d rows): at most 62", what, bits, bits);
+  DNM_CHECK(sub->site_perm == nullptr, "%s: site_perm given for a subspace that is not SpinConserve", what);
+  DNM_CHECK(sub->vec_swizzle == 0 || (sub->vec_swizzle >= 5 && sub->vec_swizzle <= 24),
+            "%s: vec_swizzle %d: the shift of a swizzled vector lies in [5, 24]", what, sub->vec_swizzle);
+  if (sub->type == DNM_PARITY) DNM_CHECK(sub->space == 0 || sub->space == 1, "%s: parity space must be 0 or 1", what);
+  DNM_CHECK(ncols >= 1 && ncols <= 63, "%s: %d columns (1 to 63 in one call)", what, ncols);
+  for (int c = 0; cols && c < ncols; ++c) {
+    const int site = cols[2 * c], kind = cols[2 * c + 1];
+    DNM_CHECK(site >= 0 && site < sub->L, "%s: column %d has site %d outside [0, %lld)", what, c, site,
+              (long long)sub->L);
+    DNM_CHECK(kind >= PAULI_X && kind <= PAULI_Z, "%s: column %d has kind %d (1 flip, 2 flip and sign, 3 sign)", what, c,
+              kind);
+  }
+  return 0;
+}
+
+int dnm_pauli_moments_plan(const dnm_subspace *sub, int ncols, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                           size_t *lds_bytes, size_t *scratch_bytes) {
+  DNM_TRY(pauli_check(sub, ncols, nullptr));
+  GramPlan p;
+  // (the bond-swap sweep's panel rule and workgroup count: inherited, not measured for this fill)
+  DNM_TRY(swap_plan(sub->type, (int)sub->L, 0, ncols, 0, &p, "Pauli"));
+  plan_out(p.nb, p.B, p.nwg, p.lds_bytes, p.partial_bytes, tile_rows, panel_rows_log2, nworkgroups, lds_bytes,
+           scratch_bytes);
+  return 0;
+}
+
+int dnm_pauli_moments(const void *x, const dnm_subspace *sub, int ncols, const int32_t *cols, double *out,
+                      void *stream) {
+  DNM_CHECK(x && out && cols, "Pauli moments: null argument");
+  DNM_TRY(pauli_check(sub, ncols, cols));
+  const int L = (int)sub->L;
+  GramPlan p;
+  DNM_TRY(swap_plan(sub->type, L, 0, ncols, 0, &p, "Pauli"));
+  DNM_TRY(gram_moments(p, L, (size_t)ncols + 1, "Pauli moments", out, stream,
+                       [&](int64_t *, void *partial, void *G) {
+    return launch_pauli_moments(x, sub->type, L, (int)sub->space, sub->vec_swizzle, ncols, cols, p, partial, G,
+                                S(stream));
+  }));
+  if (sub->type == DNM_PARITY) {
+    // a flipping column holds the rows of the opposite sector: its products with the columns that do not flip (the
+    // state's own among them) vanish by symmetry
+    const size_t D = (size_t)ncols + 1;
+    auto flips = [&](size_t col) { return col > 0 && pauli_flips(cols[2 * (col - 1) + 1]); };
+    for (size_t i = 0; i < D; ++i)
+      for (size_t j = 0; j < D; ++j)
+        if (flips(i) != flips(j)) out[2 * (i * D + j)] = out[2 * (i * D + j) + 1] = 0.0;
+  }
+  return 0;
+}
+
+int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t *cols, int64_t n, const int64_t *rows,
+                              int64_t *idx, int8_t *sign) {
+  DNM_CHECK(cols, "Pauli partner indices: null argument");
+  DNM_TRY(pauli_check(sub, ncols, cols));
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "Pauli partner indices: null argument");
+  const bool parity = sub->type == DNM_PARITY;
+  const int64_t nrows = (int64_t)1 << ((int)sub->L - (parity ? 1 : 0));
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t row = rows[i];
+    DNM_CHECK(row >= 0 && row < nrows, "Pauli partner indices: row %lld of %lld rows", (long long)row,
+              (long long)nrows);
+    const int par = hd_par((uint64_t)row);
+    for (int c = 0; c < ncols; ++c) {
+      const int site = cols[2 * c], kind = cols[2 * c + 1];
+      const uint64_t cfg = pauli_row_config(parity, (int)sub->space, (uint64_t)row, par, pauli_flips(kind));
+      idx[i * ncols + c] = row ^ (int64_t)pauli_index_mask(parity, site, kind);
+      sign[i * ncols + c] = (int8_t)(pauli_negative(cfg, site, kind) ? -1 : 1);
     }
   }
   return 0;

@@ -286,6 +286,22 @@ class State:
         from . import computations
         return computations.chirality_correlations(self, triangles, connected=connected)
 
+    def pauli_correlations(self, sites=None):
+        """``(one, two)``: every <sigma^a_i> and <sigma^a_i sigma^b_j>, a, b in x, y, z, in one pass
+        -> computations.pauli_correlations."""
+        from . import computations
+        return computations.pauli_correlations(self, sites=sites)
+
+    def two_site_density_matrices(self, pairs=None):
+        """The reduced density matrices of pairs of spins from one pass -> computations.two_site_density_matrices."""
+        from . import computations
+        return computations.two_site_density_matrices(self, pairs=pairs)
+
+    def mutual_information(self, sites=None):
+        """``I[i, j]`` = S_i + S_j - S_ij for every pair of spins from one pass -> computations.mutual_information."""
+        from . import computations
+        return computations.mutual_information(self, sites=sites)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

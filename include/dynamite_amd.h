@@ -312,6 +312,43 @@ int dnm_cyc_moments(const void *x, const dnm_subspace *sub, int xparity_sector, 
                     double *out, void *stream);
 int dnm_cyc_partner_indices(const dnm_subspace *sub, int xparity_sector, int ncycles, const int32_t *cycles, int64_t n,
                             const int64_t *rows, int64_t *idx, int8_t *sign);
+/* Every two-spin Pauli correlator of a state without a U(1) symmetry in one pass over it (no counterpart in the
+ * reference, whose users call Operator.expectation once per pair).  A single-site Pauli applied to x is one partner
+ * amplitude times a sign: with s_j(r) = (-1)^(bit j of r), (sigmax_j x)(r) = x(r ^ e_j), (sigmaz_j x)(r) = s_j(r) x(r) and
+ * (sigmay_j x)(r) = -i s_j(r) x(r ^ e_j).  For ncols columns (site j_c, kind_c) = (cols[2 c], cols[2 c + 1]) -- kind 1:
+ * flip (sigma-x), 2: flip and sign (sigma-y up to the phase -i, which the caller applies), 3: sign (sigma-z); a column
+ * may repeat, columns may share a site -- and the operand matrix over the rows q of the vector
+ *   A[q][0] = x[q],   A[q][1 + c] = (-1)^(g_c * bit j_c of r_c(q)) x[q ^ m_c]     (f_c: kind 1 or 2, g_c: kind 2 or 3)
+ *   G = A^H A      ((ncols + 1) x (ncols + 1) complex128, row-major, Hermitian):
+ * G[0][0] = <x|x> and, up to the phases, G[0][1 + c] = <sigma_c> and G[1 + c][1 + c'] = <sigma_c sigma_c'>.  Full: r_c(q) =
+ * q and m_c = f_c << j_c.  Parity(space): the index is the configuration without site 0, m_c = (f_c << j_c) >> 1 (a flip
+ * of site 0 pairs a row with the amplitude at its own index); a column that does not flip, column 0 among them, reads
+ * the signs of the row's own configuration (q << 1) | (par(q) ^ space), a flipping column those of the opposite sector's,
+ * (q << 1) | (par(q) ^ space ^ 1); the entries of G between a flipping and a non-flipping column vanish by symmetry and
+ * are exact zeros.  Sums are raw (nothing is normalised).  G equals its conjugate transpose to the last bit, its
+ * diagonal is real, and two calls return the same bits on any device (no atomics; the number of workgroups follows
+ * from the number of rows alone).
+ * x (device) is the WHOLE state on one device, in index order or XOR-swizzled, read as it lies.
+ * Refused, each before any device call: null pointers, Explicit subspaces, SpinConserve subspaces (a flip leaves the
+ * sector: dnm_zz_moments and dnm_pm_moments serve them), an unknown subspace type, L outside [1, 64] or more than 62
+ * index bits, a non-null site_perm, a swizzle shift outside {0} and [5, 24], a Parity space other than 0 or 1, ncols
+ * outside [1, 63], a site outside [0, L), a kind outside {1, 2, 3}.
+ * out: HOST, (ncols + 1)^2 * 2 doubles (re, im); the call synchronises the stream like dnm_vec_dot.  Scratch comes from
+ * the library's workspace (dnm_release_workspace).
+ * dnm_pauli_moments_plan (host only, no device needed): the plan of dnm_swap_moments_plan for the same number of columns
+ * (a rule inherited from that pass, not measured for this one) -- tile_rows = ceil((ncols + 1) / 16) rows of 16 x 16
+ * tiles (NB), the panel of 2^panel_rows_log2 rows of A a workgroup stages in LDS, the workgroups of the sweep --
+ * ceil(rows / 512), at most 1024 -- the bytes of LDS of a launch (at most 152 KB) and the bytes of the partial tiles,
+ * nworkgroups * (NB (NB + 1) / 2 + NB^2) * 256 * 8; any output may be null.
+ * dnm_pauli_partner_indices (host only): for each of the n rows (reference-order indices into x; one out of range is
+ * refused) and each column, idx[row * ncols + c] = the reference-order index into x of the amplitude A[row][1 + c] is
+ * taken from and sign[row * ncols + c] its factor, +1 or -1.  The arithmetic is the kernel's (csrc/pauli_cols.h). */
+int dnm_pauli_moments_plan(const dnm_subspace *sub, int ncols, int *tile_rows, int *panel_rows_log2, int *nworkgroups,
+                           size_t *lds_bytes, size_t *scratch_bytes);
+int dnm_pauli_moments(const void *x, const dnm_subspace *sub, int ncols, const int32_t *cols, double *out,
+                      void *stream);
+int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t *cols, int64_t n, const int64_t *rows,
+                              int64_t *idx, int8_t *sign);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
