@@ -2039,6 +2039,52 @@ def pauli_moments(vec, subspace, cols):
     return out
 
 
+VEC_GRAM_MAX = 64         # vectors of one call of vec_gram
+
+
+def vec_gram_plan(nvec, n):
+    """``dnm_vec_gram_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
+    launch, bytes of the partial tiles) of the Gram sweep over ``nvec`` vectors of ``n`` elements."""
+    tr, pb, nw, lb, sb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_vec_gram_plan(int(nvec), int(n), C.byref(tr), C.byref(pb), C.byref(nw), C.byref(lb),
+                                            C.byref(sb)))
+    return tr.value, pb.value, nw.value, int(lb.value), int(sb.value)
+
+
+def vec_gram_ptrs(ptrs, n):
+    """``dnm_vec_gram`` on raw device addresses: numpy array G of shape (len(ptrs), len(ptrs)), complex128, G[a, b] =
+    sum_r conj(x_a[r]) x_b[r] over the ``n`` complex128 elements at each address (16-byte aligned; an address may
+    repeat)."""
+    nvec = len(ptrs)
+    xs = (C.c_void_p * max(nvec, 1))(*[int(p) for p in ptrs])
+    out = np.empty((nvec, nvec), dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_vec_gram(xs, nvec, int(n), out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)),
+                                       _stream()))
+    return out
+
+
+def vec_gram(vecs):
+    """The Gram matrix of the vectors ``vecs`` (a list of at most 64 ``Vec`` of equal size) in one pass over them (one
+    matrix-core kernel): numpy array G of shape (len(vecs), len(vecs)), complex128, G[a, b] = sum_r conj(x_a[r]) x_b[r]
+    = <x_a|x_b> (raw sums, nothing normalised; G is Hermitian to the last bit and its diagonal real).  Every vector is
+    brought into the layout of the first (a copy only where the layouts differ) and the sweep runs over the whole
+    array: the padding of the SpinConserve internal layout is zero, and an elementwise sum does not care about the
+    order of the rows.  A vector may appear more than once.  More than 64 vectors raise ``ValueError`` (the caller
+    cuts the list); on more than one rank this raises ``NotImplementedError``."""
+    config._initialize()
+    vecs = list(vecs)
+    if not 1 <= len(vecs) <= VEC_GRAM_MAX:
+        raise ValueError('the Gram matrix of %d vectors: 1 to %d in one call' % (len(vecs), VEC_GRAM_MAX))
+    if _dist() is not None:
+        raise NotImplementedError('the Gram matrix of partitioned vectors: the sum of the ranks\' matrices is not '
+                                  'implemented')
+    first = vecs[0]
+    if any(v.size != first.size for v in vecs):
+        raise ValueError('vectors of different sizes: %r' % sorted({v.size for v in vecs}))
+    same = [first._in_my_layout(v) for v in vecs]        # (keeps the copies alive until the call has returned)
+    return vec_gram_ptrs([v.array.data_ptr() for v in same], first.local_size)
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -1051,6 +1051,63 @@ def mutual_information(state, sites=None):
     return out
 
 
+_GRAM_CALL_MAX = 64       # vectors of one call of backend.vec_gram
+_GRAM_CHUNK = 32          # longer lists: chunks of at most this size, one call per pair of chunks
+
+
+def _gram_states(states, what):
+    """The list ``states``, checked: not empty, every state initialised, all on one subspace."""
+    states = list(states)
+    if not states:
+        raise ValueError('%s of an empty list of states' % what)
+    for s in states:
+        s.assert_initialized()
+    if any(not s.subspace.identical(states[0].subspace) for s in states[1:]):
+        raise ValueError('%s: the states must all be on the same subspace' % what)
+    return states
+
+
+def _gram_chunks(n):
+    return [np.arange(lo, min(lo + _GRAM_CHUNK, n)) for lo in range(0, n, _GRAM_CHUNK)]
+
+
+def overlap_matrix(states, others=None):
+    """The overlaps of many states from one pass over them (one matrix-core kernel, ``backend.vec_gram``) instead of
+    one ``State.dot`` -- a launch and a host synchronisation -- per pair: complex128 numpy array ``S[a, b]`` =
+    <states[a]|states[b]>, or with ``others`` of shape (len(states), len(others)), ``S[a, b]`` = <states[a]|others[b]>.
+    The inner product is conjugate-linear in its first argument and nothing is normalised.  All states must be
+    initialised and on one subspace.  Up to 64 columns in all -- ``len(states) + len(others)`` -- take one call; longer
+    lists are cut into chunks of at most 32 and every pair of chunks takes one call.  Without ``others`` the result is
+    Hermitian to the last bit and its diagonal is real, chunked or not.  States on one process."""
+    from . import backend
+    config._initialize()
+    states = _gram_states(states, 'overlap matrix')
+    if others is None:
+        n = len(states)
+        if n <= _GRAM_CALL_MAX:
+            return backend.vec_gram([s.vec for s in states])
+        S = np.zeros((n, n), dtype=np.complex128)
+        chunks = _gram_chunks(n)
+        for i in range(len(chunks)):
+            for j in range(i + 1, len(chunks)):
+                # (with more than one chunk every chunk has a partner: the diagonal blocks come with the pairs)
+                sel = np.concatenate([chunks[i], chunks[j]])
+                S[np.ix_(sel, sel)] = backend.vec_gram([states[k].vec for k in sel])
+        return S
+    others = _gram_states(others, 'overlap matrix')
+    if not others[0].subspace.identical(states[0].subspace):
+        raise ValueError('overlap matrix: the states must all be on the same subspace')
+    ns, no = len(states), len(others)
+    if ns + no <= _GRAM_CALL_MAX:
+        return backend.vec_gram([s.vec for s in states + others])[:ns, ns:].copy()
+    S = np.zeros((ns, no), dtype=np.complex128)
+    for ci in _gram_chunks(ns):
+        for cj in _gram_chunks(no):
+            g = backend.vec_gram([states[k].vec for k in ci] + [others[k].vec for k in cj])
+            S[np.ix_(ci, cj)] = g[:len(ci), len(ci):]
+    return S
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

@@ -1,11 +1,13 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
 // density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap, three-site rotation
-// (chirality) and two-spin Pauli moments.  They share the cached scratch of the partial tiles.
+// (chirality) and two-spin Pauli moments -- and the Gram matrix of many vectors, which runs on the same panel scheme.
+// They share the cached scratch of the partial tiles.
 #include "gram_tile.h"
 #include "mat.h"
 #include "pm_rank.h"
 #include "cyc_rank.h"
 #include "pauli_cols.h"
+#include "vgram.h"
 
 #include <algorithm>
 #include <cstring>
@@ -605,6 +607,44 @@ int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t 
     }
   }
   return 0;
+}
+
+// ---- Gram matrix of many vectors ----------------------------------------------------------------------------------
+// what the plan and the call check alike, before any device call
+static int vgram_check(int nvec, int64_t n) {
+  const char *what = "state Gram matrix";
+  DNM_CHECK(nvec >= 1 && nvec <= 64, "%s: %d vectors (1 to 64 in one call)", what, nvec);
+  DNM_CHECK(n >= 0, "%s: vectors of %lld elements", what, (long long)n);
+  return 0;
+}
+
+int dnm_vec_gram_plan(int nvec, int64_t n, int *tile_rows, int *panel_rows_log2, int *nworkgroups, size_t *lds_bytes,
+                      size_t *scratch_bytes) {
+  DNM_TRY(vgram_check(nvec, n));
+  GramPlan p;
+  DNM_TRY(vgram_plan(nvec, n, &p));
+  plan_out(p.nb, p.B, p.nwg, p.lds_bytes, p.partial_bytes, tile_rows, panel_rows_log2, nworkgroups, lds_bytes,
+           scratch_bytes);
+  return 0;
+}
+
+int dnm_vec_gram(const void *const *xs, int nvec, int64_t n, double *out, void *stream) {
+  const char *what = "state Gram matrix";
+  DNM_TRY(vgram_check(nvec, n));
+  DNM_CHECK(xs && out, "%s: null argument", what);
+  for (int c = 0; c < nvec; ++c) {
+    DNM_CHECK(xs[c] || n == 0, "%s: vector %d is a null pointer", what, c);
+    DNM_CHECK((uintptr_t)xs[c] % 16 == 0, "%s: vector %d at %p is not 16-byte aligned", what, c, xs[c]);
+  }
+  if (n == 0) {
+    memset(out, 0, (size_t)nvec * (size_t)nvec * 2 * sizeof(double));
+    return 0;
+  }
+  GramPlan p;
+  DNM_TRY(vgram_plan(nvec, n, &p));
+  return gram_moments(p, 0, (size_t)nvec, what, out, stream, [&](int64_t *, void *partial, void *G) {
+    return launch_vec_gram(xs, nvec, p, partial, G, S(stream));
+  });
 }
 
 }  // extern "C"

@@ -505,6 +505,59 @@ class Operator:
             self.dot(state, tmp_state)
         return state.dot(tmp_state).real
 
+    _ELEMENTS_CHUNK = 32      # bras of one Gram call, and the most images kept at once
+
+    def matrix_elements(self, kets, bras=None, batch=None):
+        r"""``M[m, n]`` = <bras[m]|A|kets[n]> for lists of states, ``bras = kets`` by default: complex128 numpy array of
+        shape (len(bras), len(kets)), nothing normalised -- the off-diagonal matrix elements of a set of eigenvectors
+        in len(kets) multiplies and a few Gram passes (``backend.vec_gram``) instead of one multiply and one
+        ``State.dot`` per pair.  The kets lie on a right subspace of the operator and the bras on the matching left
+        one; otherwise this raises what ``Operator.dot`` raises.  The images A|ket> are computed with ``Operator.dot``
+        (the kets and the images adopt the operator's layout as they do there) into at most ``batch`` reusable result
+        states, at most 32; default: 32, lowered until ``batch * 16 * alloc_size`` bytes are at most half of the free
+        device memory, and never below 1.  The bras are taken in chunks of at most 32, and one Gram call covers each
+        (chunk of bras, batch of images): ``M`` is its off-diagonal block.  The bra-bra and the image-image block of
+        each call are computed and dropped; a rectangular A^H B core that would avoid this is out of scope here."""
+        kets = list(kets)
+        bras = kets if bras is None else list(bras)
+        if not kets or not bras:
+            raise ValueError('matrix elements of an empty list of states')
+        for s in kets + bras:
+            s.assert_initialized()
+        for group in (kets, bras):
+            if any(not s.subspace.identical(group[0].subspace) for s in group[1:]):
+                raise ValueError('matrix elements: the kets must all be on one subspace, and so must the bras')
+        if batch is not None and int(batch) < 1:
+            raise ValueError('matrix elements: batch must be at least 1')
+        left = bras[0].subspace
+
+        def image_state():
+            return State(L=left.L, subspace=left)
+
+        # (the first multiply raises for subspaces the operator lacks, before anything is sized)
+        pool = [self.dot(kets[0], result=image_state())]
+        if batch is None:
+            import torch
+            free = torch.cuda.mem_get_info()[0]
+            batch = self._ELEMENTS_CHUNK
+            while batch > 1 and batch * 16 * pool[0].vec.alloc_size > free // 2:
+                batch -= 1
+        batch = min(int(batch), self._ELEMENTS_CHUNK)
+        M = np.empty((len(bras), len(kets)), dtype=np.complex128)
+        for k0 in range(0, len(kets), batch):
+            part = kets[k0:k0 + batch]
+            while len(pool) < len(part):
+                pool.append(image_state())
+            for n, ket in enumerate(part):
+                if k0 + n > 0:      # (the image of the first ket is in hand)
+                    self.dot(ket, result=pool[n])
+            images = [s.vec for s in pool[:len(part)]]
+            for b0 in range(0, len(bras), self._ELEMENTS_CHUNK):
+                chunk = bras[b0:b0 + self._ELEMENTS_CHUNK]
+                G = backend.vec_gram([s.vec for s in chunk] + images)
+                M[b0:b0 + len(chunk), k0:k0 + len(part)] = G[:len(chunk), len(chunk):]
+        return M
+
     # ------------------------------------------------------------------ algebra
     def _check_compatible(self, o):
         if self.L != o.L:

@@ -302,6 +302,13 @@ class State:
         from . import computations
         return computations.mutual_information(self, sites=sites)
 
+    @staticmethod
+    def overlap_matrix(states, others=None):
+        """``S[a, b]`` = <states[a]|states[b]> (or <states[a]|others[b]>) for lists of states from one pass
+        -> computations.overlap_matrix."""
+        from . import computations
+        return computations.overlap_matrix(states, others=others)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

@@ -349,6 +349,28 @@ int dnm_pauli_moments(const void *x, const dnm_subspace *sub, int ncols, const i
                       void *stream);
 int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t *cols, int64_t n, const int64_t *rows,
                               int64_t *idx, int8_t *sign);
+/* The Gram matrix of many vectors in one pass over them (no counterpart in the reference, whose users take the overlaps
+ * of a set of eigenvectors one State.dot at a time): for 1 <= nvec <= 64 device vectors of n complex128 elements each
+ *   G[a][b] = sum_r conj(x_a[r]) x_b[r]      (nvec x nvec complex128, row-major, Hermitian),
+ * conjugate-linear in the first index, nothing normalised.  With the images O x_n among the vectors the off-diagonal
+ * block of G holds the matrix elements <m|O|n>.  The vectors are separate allocations at any 16-byte-aligned addresses;
+ * a pointer may appear more than once.  The sum is elementwise, so any layout serves as long as all vectors share it
+ * and its padding is zero.  G equals its conjugate transpose to the last bit, its diagonal is real, and two calls return
+ * the same bits on any device (no atomics; the number of workgroups follows from (nvec, n) alone).
+ * xs: HOST array of nvec device pointers.  Refused, each before any device call: nvec outside [1, 64], n < 0, null xs
+ * or out, a null element of xs when n > 0, an address that is not 16-byte aligned.  n == 0 returns a zero matrix
+ * without a launch.
+ * out: HOST, nvec^2 * 2 doubles (re, im); the call synchronises the stream like dnm_vec_dot.  Scratch comes from the
+ * library's workspace (dnm_release_workspace).
+ * dnm_vec_gram_plan (host only, no device needed): tile_rows = ceil(nvec / 16) rows of 16 x 16 tiles (NB), the panel of
+ * 2^panel_rows_log2 rows a workgroup stages in LDS (this sweep's own rule: 2^7 at one and two tile rows, 2^6 at three
+ * and four, so that a wavefront holds its part of the next panel in registers while it multiplies), the workgroups of
+ * the sweep -- ceil(n / 512), at most 1024, at least one -- the bytes of LDS of a launch, (16 NB + 1) * 16 <<
+ * panel_rows_log2, and the bytes of the partial tiles, nworkgroups * (NB (NB + 1) / 2 + NB^2) * 256 * 8; any output may
+ * be null. */
+int dnm_vec_gram_plan(int nvec, int64_t n, int *tile_rows, int *panel_rows_log2, int *nworkgroups, size_t *lds_bytes,
+                      size_t *scratch_bytes);
+int dnm_vec_gram(const void *const *xs, int nvec, int64_t n, double *out, void *stream);
 /* MATOP_DESTROY -> MatDestroyCtx_GPU (bcuda_template_2.cu:110-139) */
 int dnm_mat_destroy(dnm_mat *A);
 /* MatGetSize / MatGetLocalSize */
