@@ -115,9 +115,19 @@ static int rdm_check_keep(int L, int keep_size, const int64_t *keep, int cap, co
   return 0;
 }
 
+// widest subspace of a dense reduced density matrix: a condition, not a measurement -- 16 times the 2^36 fetches of the
+// widest subspaces a device holds
+constexpr int RDM_MAX_SPINS = 40;
+
 int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size, const int64_t *keep,
                                void *rho, void *stream) {
   DNM_CHECK(x && sub && rho && keep_size >= 0 && (keep_size == 0 || keep), "null argument");
+  // every entry of rho sums over the 2^(L - keep_size) traced configurations, whatever the dimension of the subspace
+  // (rdm_plan): on a wide subspace of few states (SpinConserve(63, 2): 1953 of them) the call would not end.  The widest
+  // subspaces a device holds have 36 spins; refused before anything touches the device
+  DNM_CHECK(sub->L <= RDM_MAX_SPINS, "reduced density matrix on L=%lld spins: the kernel fetches 2^L = 2^%lld amplitudes "
+            "(2^(L - %d) traced configurations for each of the 2^%d kept ones) whatever the dimension of the subspace; "
+            "at most L=%d", (long long)sub->L, (long long)sub->L, keep_size, keep_size, RDM_MAX_SPINS);
   SubOwned s;
   DNM_TRY(s.init(sub, true));
   const int L = s.host.L;

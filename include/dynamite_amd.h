@@ -177,7 +177,9 @@ int dnm_check_conserves(int64_t nmasks, const int64_t *masks, const int64_t *mas
  * (bpetsc_impl.h:52-63, bpetsc_template_1.c:87-165, bpetsc.pyx:245-276): the density
  * matrix of the spins keep[0] < keep[1] < ... of the state x (device pointer, the
  * whole vector), all other spins traced out.  rho: device buffer of 4^keep_size
- * complex128, row-major, bit i of a row/column index = spin keep[i]. */
+ * complex128, row-major, bit i of a row/column index = spin keep[i].
+ * The kernel walks the 2^(L - keep_size) traced configurations of every kept one, whatever the dimension of the
+ * subspace: a subspace of more than 40 spins is refused (before anything touches the device). */
 int dnm_reduced_density_matrix(const void *x, const dnm_subspace *sub, int keep_size,
                                const int64_t *keep, void *rho, void *stream);
 /* The same matrix block by block, for a state of fixed magnetisation: sub is SpinConserve(L, k) and x either the
