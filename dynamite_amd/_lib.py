@@ -151,6 +151,13 @@ SIGNATURES = {
     "dnm_pauli_moments": (C.c_int, [vp, C.POINTER(Subspace), C.c_int, C.POINTER(C.c_int32), f64p, vp]),
     "dnm_pauli_partner_indices": (C.c_int, [C.POINTER(Subspace), C.c_int, C.POINTER(C.c_int32), C.c_int64, i64p, i64p,
                                             C.POINTER(C.c_int8)]),
+    "dnm_perm_plan": (C.c_int, [C.POINTER(Subspace), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                C.POINTER(C.c_size_t)]),
+    "dnm_perm_partner_indices": (C.c_int, [C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int64,
+                                           i64p, i64p, C.POINTER(C.c_int8)]),
+    "dnm_perm_apply": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, C.c_int,
+                                 vp]),
+    "dnm_perm_dots": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, vp]),
     "dnm_vec_gram_plan": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dnm_vec_gram": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int64, f64p, vp]),

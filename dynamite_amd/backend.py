@@ -1980,6 +1980,123 @@ def cyc_moments(vec, subspace, cycles, xparity_sector=0):
     return out
 
 
+PERM_MAX = 64             # permutations of one call of perm_apply / perm_dots
+
+
+def _perms_c(perms, L):
+    perms = np.ascontiguousarray(perms, dtype=np.int32)
+    if perms.ndim == 1:
+        perms = perms.reshape(1, -1)
+    if perms.ndim != 2 or perms.shape[1] != int(L):
+        raise ValueError('site permutations of %d sites must be arrays of that length, not of shape %r'
+                         % (int(L), perms.shape))
+    return perms, perms.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def perm_plan(sub_c, nperm):
+    """``dnm_perm_plan`` (host only): (workgroups, bytes of LDS of a launch, bytes of scratch of ``perm_dots``) of the
+    site-permutation pass with ``nperm`` permutations over a state of the subspace."""
+    nw, lb, sb = C.c_int(), C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_perm_plan(C.byref(sub_c), int(nperm), C.byref(nw), C.byref(lb), C.byref(sb)))
+    return nw.value, int(lb.value), int(sb.value)
+
+
+def perm_partner_indices(sub_c, perms, rows, xparity_sector=0):
+    """``dnm_perm_partner_indices`` (host only): ``(idx, sign)``, int64 and int8 arrays (len(rows), len(perms)) -- for
+    the row at position ``rows[n]`` of the vector as it lies (the reference-order index unless a Full / Parity
+    descriptor carries a swizzle) and the site permutation pi_g, the position of the amplitude of the source
+    configuration (bit i of the source = bit pi_g(i) of the row's), and its factor: +1, or ``xparity_sector`` where bit
+    L - 1 of the source is set and the amplitude is the complement's."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    perms, pp = _perms_c(perms, sub_c.L)
+    idx = np.empty((rows.size, perms.shape[0]), dtype=np.int64)
+    sign = np.empty((rows.size, perms.shape[0]), dtype=np.int8)
+    _lib.check(_lib.lib().dnm_perm_partner_indices(C.byref(sub_c), int(xparity_sector), perms.shape[0], pp, rows.size,
+                                                   _lib.p64(rows), _lib.p64(idx),
+                                                   sign.ctypes.data_as(C.POINTER(C.c_int8))))
+    return idx, sign
+
+
+def _perm_operands(vecs, sub_c, nperm, xparity_sector, what):
+    """The device tensors of ``vecs`` in one layout the pass reads -- that of the first, SpinConserve vectors in
+    reference order -- and the descriptor saying so."""
+    if _dist() is not None:
+        raise NotImplementedError('%s of a partitioned state: the source amplitudes of a rank\'s rows lie on other '
+                                  'ranks' % what)
+    first = vecs[0]
+    if not first.internal:
+        # (refused descriptors never get as far as a copy of a vector)
+        _lib.check(_lib.lib().dnm_perm_plan(C.byref(sub_c), int(nperm), None, None, None))
+    out, d = [], sub_c
+    for v in vecs:
+        x, d = _reference_order(first._in_my_layout(v), sub_c)
+        out.append(x)
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(d), C.byref(full)))
+    expect = full.value // 2 if xparity_sector else full.value
+    for x in out:
+        if x.numel() != expect:
+            raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), expect))
+    return out, d
+
+
+def perm_apply(vec, subspace, perms, coef, result, xparity_sector=0, accumulate=False):
+    """``result`` = (``result`` if ``accumulate`` else 0) + sum_g coef[g] P_g ``vec`` for the n <= 64 site permutations
+    ``perms`` (int array (n, L); P_pi moves the spin at site i to site pi(i), so (P_pi psi)(c') = psi(c) with bit i of c
+    = bit pi(i) of c') in one pass (``dnm_perm_apply``); n = 1 with coef = [1] is the plain permutation, bit for bit.
+    ``subspace`` is the descriptor of the Full, Parity or SpinConserve subspace of the vectors -- with
+    ``xparity_sector`` = +-1 that of the parent of the XParity subspace whose representatives they hold.  ``result``
+    is another vector of the same size: the pass gathers.  Swizzled Full / Parity vectors are read and written as they
+    lie; a SpinConserve vector in the internal layout is converted to reference order first and the result is written
+    in reference order to a scratch vector and brought home (one extra vector each).  On more than one rank this
+    raises ``NotImplementedError``."""
+    import torch
+    config._initialize()
+    if result is vec:
+        raise ValueError('site permutations: the result must be another vector than the state (the pass gathers)')
+    if result.size != vec.size:
+        raise ValueError('site permutations: a result of %d elements for a state of %d' % (result.size, vec.size))
+    sub_c = subspace['data']
+    perms, pp = _perms_c(perms, sub_c.L)
+    n = perms.shape[0]
+    coef = np.ascontiguousarray(coef, dtype=np.complex128).reshape(-1)
+    if coef.size != n:
+        raise ValueError('site permutations: %d coefficients for %d permutations' % (coef.size, n))
+    (x,), d = _perm_operands([vec], sub_c, n, xparity_sector, 'site permutations')
+    if result.internal:
+        y = result.local_natural() if accumulate else torch.empty(result.rows, dtype=x.dtype, device=x.device)
+    else:
+        if result.swz != (0 if vec.internal else vec.swz):
+            raise ValueError('vectors of different layouts (%r, %r)' % (vec.layout, result.layout))
+        y = result.array
+    _lib.check(_lib.lib().dnm_perm_apply(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.byref(d),
+                                         int(xparity_sector), n, pp,
+                                         coef.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)),
+                                         int(bool(accumulate)), _stream()))
+    if result.internal:
+        result.set_local_natural(y)
+    return result
+
+
+def perm_dots(phi, psi, subspace, perms, xparity_sector=0):
+    """<phi|P_g|psi> = sum_r conj(phi[r]) (P_g psi)[r] for the n <= 64 site permutations ``perms`` in one pass over the
+    two vectors (``dnm_perm_dots``): numpy array (n,), complex128, raw sums, nothing normalised; two calls return the
+    same bits.  Conventions, ``subspace`` and ``xparity_sector`` as for ``perm_apply`` (under XParity the sum runs over
+    the representatives, with no factor 2); ``phi`` may be ``psi``.  A SpinConserve vector in the internal layout is
+    converted to reference order first (one extra vector each).  On more than one rank this raises
+    ``NotImplementedError``."""
+    config._initialize()
+    sub_c = subspace['data']
+    perms, pp = _perms_c(perms, sub_c.L)
+    n = perms.shape[0]
+    xs, d = _perm_operands([psi] if phi is psi else [psi, phi], sub_c, n, xparity_sector, 'site permutations')
+    out = np.empty(n, dtype=np.complex128)
+    _lib.check(_lib.lib().dnm_perm_dots(C.c_void_p(xs[-1].data_ptr()), C.c_void_p(xs[0].data_ptr()), C.byref(d),
+                                        int(xparity_sector), n, pp,
+                                        out.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), _stream()))
+    return out
+
+
 def _pauli_cols_c(cols):
     cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, 2)
     return cols, cols.ctypes.data_as(C.POINTER(C.c_int32))

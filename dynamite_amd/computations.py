@@ -1108,6 +1108,124 @@ def overlap_matrix(states, others=None):
     return S
 
 
+_PERM_CALL_MAX = 64       # permutations of one call of backend.perm_apply / backend.perm_dots
+
+
+def _site_perms(state, perms, what, single=False):
+    """(subspace whose ``_to_c()`` the pass takes, XParity sector or 0, int32 array (G, L)) for a state and a site
+    permutation (``single``) or a list of them, checked: the right length, every row a bijection of [0, L)."""
+    state.assert_initialized()
+    sp, sector = _swap_subspace(state, what)
+    L = sp.L
+    perms = np.asarray(perms)
+    if single:
+        if perms.ndim != 1:
+            raise ValueError('%s: a site permutation is a one-dimensional array, not one of shape %r'
+                             % (what, perms.shape))
+        perms = perms.reshape(1, -1)
+    if perms.size == 0:
+        raise ValueError('%s of an empty list of permutations' % what)
+    if perms.ndim != 2 or perms.shape[1] != L:
+        raise ValueError('%s: a site permutation of %d sites has length %d, not an array of shape %r'
+                         % (what, L, L, perms.shape))
+    if not np.issubdtype(perms.dtype, np.integer):
+        raise ValueError('%s: site permutations are arrays of integers' % what)
+    if not np.array_equal(np.sort(perms, axis=1), np.broadcast_to(np.arange(L), perms.shape)):
+        bad = int(np.flatnonzero(np.any(np.sort(perms, axis=1) != np.arange(L), axis=1))[0])
+        raise ValueError('%s: permutation %d is not a bijection of [0, %d) (a site outside the range, or a repeated '
+                         'site)' % (what, bad, L))
+    return sp, sector, np.ascontiguousarray(perms, dtype=np.int32)
+
+
+def _perm_result(state, result, what):
+    from .states import State
+    if result is state:
+        raise ValueError('%s: the result must be another state than the input (the pass gathers)' % what)
+    if result is None:
+        result = State(L=state.L, subspace=state.subspace)
+    elif result.subspace != state.subspace:
+        raise ValueError('subspace of state and result must match')
+    return result
+
+
+def permute_sites(state, perm, result=None):
+    """P_pi|state> for the site permutation ``perm`` = pi, an int array of length L and a bijection of [0, L): P_pi moves
+    the spin at site i to site pi(i), P_pi|c> = |c'> with c'_{pi(i)} = c_i, so (P_pi psi)(c') = psi(c) where the source
+    configuration c has bit i equal to bit pi(i) of c'; hence P_pi sigma^a_i P_pi^H = sigma^a_{pi(i)}.  One gather pass on
+    the device (``backend.perm_apply``), which rounds nothing: the result holds the bits of the state.  A permutation
+    keeps the number of up spins and the parity and commutes with the global flip: Full, Parity and SpinConserve states
+    and XParity over those, on one process; Explicit and Auto are refused.  ``result``: a state on the same subspace to
+    write into -- not ``state`` itself, which raises ``ValueError``."""
+    from . import backend
+    config._initialize()
+    sp, sector, perms = _site_perms(state, perm, 'site permutation', single=True)
+    result = _perm_result(state, result, 'site permutation')
+    backend.perm_apply(state.vec, sp._to_c(), perms, [1.0], result.vec, sector)
+    result.set_initialized()
+    return result
+
+
+def symmetrize(state, perms, characters=None, result=None):
+    """(1 / G) sum_g conj(chi_g) P_g|state> for the G site permutations ``perms`` (the convention of ``permute_sites``)
+    and the characters ``characters`` = chi, all ones when None: with the elements of a group and the characters of a
+    one-dimensional representation, the projection of the state onto it -- e.g. ``lattices.chain_translations(L)`` with
+    chi_g = exp(-2 pi i k g / L) for the momentum 2 pi k / L, in which P_1 has the eigenvalue chi_1.  One pass over the
+    state per 64 permutations (``backend.perm_apply``), the later ones accumulating.  Nothing is normalised.  Subspaces
+    and ``result`` as for ``permute_sites``."""
+    from . import backend
+    config._initialize()
+    sp, sector, perms = _site_perms(state, perms, 'symmetrize')
+    G = perms.shape[0]
+    chi = np.ones(G, dtype=np.complex128) if characters is None else np.asarray(characters, dtype=np.complex128).reshape(-1)
+    if chi.size != G:
+        raise ValueError('symmetrize: %d characters for %d permutations' % (chi.size, G))
+    result = _perm_result(state, result, 'symmetrize')
+    coef = chi.conj() / G
+    sub_c = sp._to_c()
+    for lo in range(0, G, _PERM_CALL_MAX):
+        hi = min(lo + _PERM_CALL_MAX, G)
+        backend.perm_apply(state.vec, sub_c, perms[lo:hi], coef[lo:hi], result.vec, sector, accumulate=lo > 0)
+    result.set_initialized()
+    return result
+
+
+def symmetry_expectations(state, perms, other=None):
+    """<other|P_g|state> for every site permutation of ``perms`` (the convention of ``permute_sites``), ``other`` being
+    ``state`` when None: complex128 numpy array of shape (G,), nothing normalised, as ``expectation`` normalises
+    nothing.  One pass over the two states per 64 permutations (``backend.perm_dots``); two calls return the same
+    bits.  With the elements of the space group of a lattice these are the numbers that label an eigenstate by momentum
+    and point-group quantum number.  Subspaces as for ``permute_sites``; ``other`` must be on the subspace of
+    ``state``."""
+    from . import backend
+    config._initialize()
+    sp, sector, perms = _site_perms(state, perms, 'symmetry expectations')
+    if other is None:
+        other = state
+    else:
+        other.assert_initialized()
+        if not other.subspace.identical(state.subspace):
+            raise ValueError('symmetry expectations: the two states must be on the same subspace')
+    sub_c = sp._to_c()
+    out = [backend.perm_dots(other.vec, state.vec, sub_c, perms[lo:lo + _PERM_CALL_MAX], sector)
+           for lo in range(0, perms.shape[0], _PERM_CALL_MAX)]
+    return np.concatenate(out)
+
+
+def symmetry_representation(states, perms):
+    """``D[g, m, n]`` = <states[m]|P_g|states[n]> for a list of N states -- a multiplet -- and G site permutations (the
+    convention of ``permute_sites``): complex128 numpy array of shape (G, N, N), nothing normalised; for an orthonormal
+    basis of an invariant space, the matrices of the representation it carries, whose traces are its characters.  One
+    ``symmetry_expectations`` per pair of states.  All states must be initialised and on one subspace."""
+    states = _gram_states(states, 'symmetry representation')
+    _, _, perms = _site_perms(states[0], perms, 'symmetry representation')
+    N = len(states)
+    D = np.empty((perms.shape[0], N, N), dtype=np.complex128)
+    for m in range(N):
+        for n in range(N):
+            D[:, m, n] = symmetry_expectations(states[n], perms, other=states[m])
+    return D
+
+
 def _entropy_of_spectrum(w):
     log = np.zeros(w.shape)
     np.log(w, where=w > 0, out=log)

@@ -1,12 +1,14 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
 // density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap, three-site rotation
-// (chirality) and two-spin Pauli moments -- and the Gram matrix of many vectors, which runs on the same panel scheme.
-// They share the cached scratch of the partial tiles.
+// (chirality) and two-spin Pauli moments -- the Gram matrix of many vectors, which runs on the same panel scheme, and
+// the site permutations of a state (two plain gather kernels, no panel).  They share the cached scratch of the partial
+// tiles.
 #include "gram_tile.h"
 #include "mat.h"
 #include "pm_rank.h"
 #include "cyc_rank.h"
 #include "pauli_cols.h"
+#include "perm.h"
 #include "vgram.h"
 
 #include <algorithm>
@@ -617,6 +619,99 @@ int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t 
     }
   }
   return 0;
+}
+
+// ---- site permutations ----------------------------------------------------------------------------------------------
+// what the plan, the calls and the partner table check alike, before any device call (perms: null for the plan)
+static int perm_check(const dnm_subspace *sub, int xsec, int nperm, const int32_t *perms, PermPlan *p,
+                      std::vector<unsigned char> *tables) {
+  const char *what = "site permutations";
+  DNM_TRY(swap_check_subspace(sub, xsec, what));
+  DNM_CHECK(nperm >= 1 && nperm <= PERM_MAX, "%s: %d permutations (1 to %d in one call)", what, nperm, PERM_MAX);
+  DNM_TRY(perm_plan(sub->type, (int)sub->L, (int)sub->k, nperm, xsec, p));
+  if (perms) {
+    tables->resize(p->lds_bytes);
+    int bad = 0;
+    DNM_CHECK(perm_fill_tables(*p, (int)sub->L, nperm, perms, tables->data(), &bad),
+              "%s: permutation %d is not a bijection of [0, %lld)", what, bad, (long long)sub->L);
+  }
+  return 0;
+}
+
+int dnm_perm_plan(const dnm_subspace *sub, int nperm, int *nworkgroups, size_t *lds_bytes, size_t *scratch_bytes) {
+  PermPlan p;
+  DNM_TRY(perm_check(sub, 0, nperm, nullptr, &p, nullptr));
+  plan_out(0, 0, p.nwg, p.lds_bytes, p.lds_bytes + p.partial_bytes + 2 * (size_t)nperm * sizeof(double), nullptr,
+           nullptr, nworkgroups, lds_bytes, scratch_bytes);
+  return 0;
+}
+
+int dnm_perm_partner_indices(const dnm_subspace *sub, int xparity_sector, int nperm, const int32_t *perms, int64_t n,
+                             const int64_t *rows, int64_t *idx, int8_t *sign) {
+  DNM_CHECK(perms, "site permutation partner indices: null argument");
+  PermPlan p;
+  std::vector<unsigned char> tables;
+  DNM_TRY(perm_check(sub, xparity_sector, nperm, perms, &p, &tables));
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "site permutation partner indices: null argument");
+  const int L = (int)sub->L, swz = sub->vec_swizzle;
+  const bool sc = sub->type == DNM_SPIN_CONSERVE, parity = sub->type == DNM_PARITY;
+  const int64_t *tab = reinterpret_cast<const int64_t *>(tables.data());
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t row = rows[i];
+    DNM_CHECK(row >= 0 && row < p.nrows, "site permutation partner indices: row %lld of %lld rows", (long long)row,
+              (long long)p.nrows);
+    const uint64_t cfg = sc ? pm_unrank(row, L, p.K, tab, L + 1)
+                            : perm_index_config(parity, (int)sub->space, (uint64_t)vec_pos(row, swz));
+    for (int g = 0; g < nperm; ++g) {
+      const uint64_t src = perm_source(cfg, tables.data() + (size_t)p.ntab * 8 + (size_t)g * PERM_LD);
+      int fl = 0;
+      idx[i * nperm + g] = sc ? perm_sc_index(src, L, p.dim, xparity_sector, tab, L + 1, &fl)
+                              : vec_pos(perm_xor_index(src, parity, L, xparity_sector, &fl), swz);
+      sign[i * nperm + g] = (int8_t)(fl ? xparity_sector : 1);
+    }
+  }
+  return 0;
+}
+
+// scratch of a call ([tables | partial sums | result]) with the tables uploaded
+static int perm_scratch(const PermPlan &p, const std::vector<unsigned char> &tables, size_t more, DevBuf *big,
+                        void **scratch, void *stream) {
+  DNM_TRY(rdm_scratch(p.lds_bytes + more, big, scratch, "site permutations", 0, 0, p.nwg));
+  DNM_HIP(hipMemcpyAsync(*scratch, tables.data(), p.lds_bytes, hipMemcpyHostToDevice, S(stream)));
+  return 0;
+}
+
+int dnm_perm_apply(const void *x, void *y, const dnm_subspace *sub, int xparity_sector, int nperm, const int32_t *perms,
+                   const double *coef, int accumulate, void *stream) {
+  DNM_CHECK(x && y && perms && coef, "site permutations: null argument");
+  DNM_CHECK(x != y, "site permutations: x and y are the same vector (the pass gathers: the result needs its own)");
+  PermPlan p;
+  std::vector<unsigned char> tables;
+  DNM_TRY(perm_check(sub, xparity_sector, nperm, perms, &p, &tables));
+  DevBuf big;
+  void *scratch = nullptr;
+  DNM_TRY(perm_scratch(p, tables, 0, &big, &scratch, stream));
+  DNM_TRY(launch_perm_apply(x, y, sub->type, (int)sub->L, (int)sub->space, sub->vec_swizzle, xparity_sector, nperm, coef,
+                            accumulate != 0, p, scratch, S(stream)));
+  DNM_HIP(hipStreamSynchronize(S(stream)));     // the host tables and `big` are released on return
+  return 0;
+}
+
+int dnm_perm_dots(const void *phi, const void *psi, const dnm_subspace *sub, int xparity_sector, int nperm,
+                  const int32_t *perms, double *out, void *stream) {
+  DNM_CHECK(phi && psi && perms && out, "site permutations: null argument");
+  PermPlan p;
+  std::vector<unsigned char> tables;
+  DNM_TRY(perm_check(sub, xparity_sector, nperm, perms, &p, &tables));
+  const size_t obytes = 2 * (size_t)nperm * sizeof(double);
+  DevBuf big;
+  void *scratch = nullptr;
+  DNM_TRY(perm_scratch(p, tables, p.partial_bytes + obytes, &big, &scratch, stream));
+  void *partial = (char *)scratch + p.lds_bytes, *o_dev = (char *)partial + p.partial_bytes;
+  DNM_TRY(launch_perm_dots(phi, psi, sub->type, (int)sub->L, (int)sub->space, sub->vec_swizzle, xparity_sector, nperm, p,
+                           scratch, partial, o_dev, S(stream)));
+  // (synchronises: the host tables and `big` are released on return)
+  return dnm_memcpy_d2h(out, o_dev, obytes, stream);
 }
 
 // ---- Gram matrix of many vectors ----------------------------------------------------------------------------------

@@ -95,6 +95,93 @@ def kagome_triangles(cluster):
     return sorted(found)
 
 
+# ---- site permutations of the lattices' symmetries (host only) ---------------------------------------------------------
+# A site permutation is a list pi of length N, a bijection of [0, N): the spin at site i moves to site pi(i)
+# (``computations.permute_sites``).  A geometric map f of the lattice gives pi(i) = the number of the point f(point i).
+
+def chain_translations(L):
+    """The L translations of the periodic chain: the g-th is pi(i) = (i + g) mod L; the identity comes first."""
+    return [[(i + g) % L for i in range(L)] for g in range(L)]
+
+
+def chain_reflection(L):
+    """The reflection of the chain, pi(i) = L - 1 - i."""
+    return [L - 1 - i for i in range(L)]
+
+
+def square_translations(nx, ny):
+    """The nx ny translations of the periodic nx x ny square lattice (site (x, y) -> x + nx * y): the one by (a, b) at
+    place a + nx * b, the identity first."""
+    return [[(x + a) % nx + nx * ((y + b) % ny) for y in range(ny) for x in range(nx)]
+            for b in range(ny) for a in range(nx)]
+
+
+def _kagome_image(order, index, wrap, f):
+    """The site permutation of the map f of points of a kagome torus, or None where an image is not a site of it or two
+    sites share one."""
+    perm = []
+    for p in order:
+        q = wrap(f(p))
+        j = index.get(q) if _is_site(q) else None
+        if j is None:
+            return None
+        perm.append(j)
+    return perm if len(set(perm)) == len(perm) else None
+
+
+def kagome_translations(cluster):
+    """The N / 3 translations of the torus ``kagome(cluster)`` builds, with its site numbering: a list of ``((u, v),
+    perm)`` for the translation by u (2, 0) + v (0, 2) in the skew coordinates of the walk -- each distinct translation
+    once, under its lexicographically smallest (u, v) with u, v >= 0, in that order, so that the identity comes
+    first."""
+    order, index, wrap, _ = _kagome_walk(cluster)
+    n = len(order) // 3             # the order of the translation group: n times any translation is the identity
+    found, seen = [], set()
+    for u in range(n):
+        for v in range(n):
+            perm = _kagome_image(order, index, wrap, lambda p: (p[0] + 2 * u, p[1] + 2 * v))
+            if tuple(perm) not in seen:
+                seen.add(tuple(perm))
+                found.append(((u, v), perm))
+    return found
+
+
+def kagome_point_group(cluster):
+    """The elements of C6v about the hexagon centre (1, 0) that are symmetries of the torus ``kagome(cluster)`` builds,
+    with its site numbering: a list of ``((m, k), perm)`` over m = 0, 1 and k = 0..5 for k rotations by 60 degrees, (x,
+    y) -> (-y, x + y), after -- when m = 1 -- the mirror (x, y) -> (y, x), both relative to the centre.  Only the
+    elements that map the torus onto itself (the spanning vectors onto vectors of their lattice) and edges onto edges
+    are returned, the identity (0, 0) first: 12 of them on the most symmetric clusters, 2 on most."""
+    order, index, wrap, edges = _kagome_walk(cluster)
+    (a0, a1), (b0, b1) = KAGOME_CLUSTERS[cluster] if isinstance(cluster, str) else cluster
+    spanning = ((2 * a0, 2 * a1), (2 * b0, 2 * b1))
+    cx, cy = 1, 0
+
+    def linear(p, m, k):
+        x, y = (p[1], p[0]) if m else p
+        for _ in range(k):
+            x, y = -y, x + y
+        return x, y
+
+    found = []
+    for m in (0, 1):
+        for k in range(6):
+            if any(wrap(linear(s, m, k)) != (0, 0) for s in spanning):
+                continue
+
+            def f(p):
+                x, y = linear((p[0] - cx, p[1] - cy), m, k)
+                return x + cx, y + cy
+
+            perm = _kagome_image(order, index, wrap, f)
+            if perm is None:
+                continue
+            if {(min(perm[i], perm[j]), max(perm[i], perm[j])) for i, j in edges} != edges:
+                continue
+            found.append(((m, k), perm))
+    return found
+
+
 def chain(L, periodic=False):
     edges = [(i, i + 1) for i in range(L - 1)]
     if periodic and L > 2:

@@ -309,6 +309,29 @@ class State:
         from . import computations
         return computations.overlap_matrix(states, others=others)
 
+    def permute_sites(self, perm, result=None):
+        """P_pi|self> for the site permutation ``perm`` (the spin at site i moves to site perm[i])
+        -> computations.permute_sites."""
+        from . import computations
+        return computations.permute_sites(self, perm, result=result)
+
+    def symmetrize(self, perms, characters=None, result=None):
+        """(1 / G) sum_g conj(chi_g) P_g|self>: the projection onto a representation of a group of site permutations
+        -> computations.symmetrize."""
+        from . import computations
+        return computations.symmetrize(self, perms, characters=characters, result=result)
+
+    def symmetry_expectations(self, perms, other=None):
+        """<other|P_g|self> for every site permutation of ``perms`` in one pass -> computations.symmetry_expectations."""
+        from . import computations
+        return computations.symmetry_expectations(self, perms, other=other)
+
+    @staticmethod
+    def symmetry_representation(states, perms):
+        """``D[g, m, n]`` = <states[m]|P_g|states[n]> for a multiplet -> computations.symmetry_representation."""
+        from . import computations
+        return computations.symmetry_representation(states, perms)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

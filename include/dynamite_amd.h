@@ -351,6 +351,46 @@ int dnm_pauli_moments(const void *x, const dnm_subspace *sub, int ncols, const i
                       void *stream);
 int dnm_pauli_partner_indices(const dnm_subspace *sub, int ncols, const int32_t *cols, int64_t n, const int64_t *rows,
                               int64_t *idx, int8_t *sign);
+/* Site permutations of a state -- lattice translations, rotations, mirrors -- in one pass over it (no counterpart in the
+ * reference, whose users take the state to the host, gather with numpy and copy it back).  A site permutation is an
+ * int32 array pi of length L, a bijection of [0, L).  P_pi moves the spin at site i to site pi(i): P_pi |c> = |c'> with
+ * c'_{pi(i)} = c_i, so (P_pi x)(c') = x(c) where the source configuration c has bit i equal to bit pi(i) of c'; hence
+ * P_pi sigma^a_i P_pi^H = sigma^a_{pi(i)}.  The rotation of dnm_cyc_moments for the triple (a, b, c) is pi(a) = b, pi(b)
+ * = c, pi(c) = a, all else fixed.  perms holds nperm such arrays, row g at perms + g * L.  With p_g(r) the index into the
+ * vector of the source of row r under permutation g and s_g(r) its factor:
+ *   dnm_perm_apply   y[r] = (accumulate ? y[r] : 0) + sum_g (coef[2 g] + i coef[2 g + 1]) s_g(r) x[p_g(r)]
+ *   dnm_perm_dots    out[g] = sum_r conj(phi[r]) s_g(r) psi[p_g(r)] = <phi|P_g|psi>
+ * nperm = 1 with coef = (1, 0) is the plain permutation, and then y holds the bits of x; with characters for
+ * coefficients the sum is a projector onto an irreducible representation.  Sums are raw (nothing is normalised).
+ * dnm_perm_dots uses no atomics and the number of workgroups follows from the number of rows alone: two calls return the
+ * same bits on any device.
+ * x, y, phi, psi (device) are WHOLE states on one device, all in one layout.  Layouts: Full / Parity in index order or
+ * XOR-swizzled, read and written as they lie; SpinConserve in reference order.  A permutation keeps the number of set
+ * bits and the parity and commutes with the global flip.  xparity_sector = +-1: the vectors hold the dim / 2 amplitudes
+ * of the representatives (bit L - 1 clear) of that XParity sector and sub is the parent's descriptor (the convention of
+ * dnm_swap_moments); a source configuration whose bit L - 1 is set is the sector's sign times the amplitude of its
+ * complement, sums run over the representatives with no factor 2, and P_pi x lies in the same sector.
+ * Refused, each before any device call: null pointers, nperm outside [1, 64], a row of perms that is not a bijection of
+ * [0, L), Explicit subspaces, an unknown subspace type, L outside [1, 64] or more than 62 index bits on Full / Parity, a
+ * non-null site_perm, the SpinConserve internal layout (the caller converts: dnm_vec_layout_copy), a Full / Parity
+ * swizzle shift outside {0} and [5, 24], xparity_sector other than 0, +1, -1, an XParity parent that cannot carry the
+ * flip (Parity with odd L, SpinConserve with L != 2 k), and x == y: the pass gathers.
+ * coef: HOST, 2 nperm doubles.  out: HOST, 2 nperm doubles (re, im).  Both calls synchronise the stream like
+ * dnm_vec_dot.  Scratch comes from the library's workspace (dnm_release_workspace).
+ * dnm_perm_plan (host only, no device needed): the workgroups of a launch -- ceil(rows / 1024), at most 4096, at least
+ * one, rows those of sub itself -- the bytes of LDS of a launch (the binomials of a SpinConserve subspace and 68 bytes
+ * per permutation) and the bytes of scratch of dnm_perm_dots; any output may be null.
+ * dnm_perm_partner_indices (host only): for each of the n rows -- positions in the vector as it lies, which are the
+ * reference-order indices unless a Full / Parity descriptor carries a swizzle -- and each permutation, idx[row * nperm +
+ * g] = the position p_g(row) of the source amplitude and sign[row * nperm + g] = s_g(row): +1, or the sector where the
+ * complement's amplitude is taken.  The arithmetic is the kernels' (csrc/perm_rank.h). */
+int dnm_perm_plan(const dnm_subspace *sub, int nperm, int *nworkgroups, size_t *lds_bytes, size_t *scratch_bytes);
+int dnm_perm_partner_indices(const dnm_subspace *sub, int xparity_sector, int nperm, const int32_t *perms, int64_t n,
+                             const int64_t *rows, int64_t *idx, int8_t *sign);
+int dnm_perm_apply(const void *x, void *y, const dnm_subspace *sub, int xparity_sector, int nperm, const int32_t *perms,
+                   const double *coef, int accumulate, void *stream);
+int dnm_perm_dots(const void *phi, const void *psi, const dnm_subspace *sub, int xparity_sector, int nperm,
+                  const int32_t *perms, double *out, void *stream);
 /* The Gram matrix of many vectors in one pass over them (no counterpart in the reference, whose users take the overlaps
  * of a set of eigenvectors one State.dot at a time): for 1 <= nvec <= 64 device vectors of n complex128 elements each
  *   G[a][b] = sum_r conj(x_a[r]) x_b[r]      (nvec x nvec complex128, row-major, Hermitian),
