@@ -132,6 +132,15 @@ SIGNATURES = {
     "dnm_zz_moments_plan": (C.c_int, [C.POINTER(Subspace), C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_size_t)]),
     "dnm_zz_moments": (C.c_int, [vp, C.POINTER(Subspace), C.c_int64, C.c_int64, f64p, vp]),
+    "dnm_born_plan": (C.c_int, [C.POINTER(Subspace), C.c_int64, i64p, i64p, C.POINTER(C.c_size_t)]),
+    "dnm_born_scan": (C.c_int, [f64p, C.c_int64, C.c_double, f64p]),
+    "dnm_born_uniforms": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, f64p, C.POINTER(C.c_uint8)]),
+    "dnm_born_block_sums": (C.c_int, [vp, C.POINTER(Subspace), C.c_int64, C.c_int64, C.c_double, f64p, f64p, vp]),
+    "dnm_born_search": (C.c_int, [vp, C.POINTER(Subspace), C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int64, f64p,
+                                  i64p, vp]),
+    "dnm_born_sample": (C.c_int, [vp, C.POINTER(Subspace), C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64,
+                                  i64p, C.POINTER(C.c_uint8), vp]),
+    "dnm_vec_power_sums": (C.c_int, [vp, C.c_int64, C.c_int, f64p, f64p, vp]),
     "dnm_pm_moments_plan": (C.c_int, [C.POINTER(Subspace), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dnm_pm_moments": (C.c_int, [vp, C.POINTER(Subspace), f64p, vp]),

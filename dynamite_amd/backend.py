@@ -1821,6 +1821,115 @@ def zz_moments(vec, subspace):
     return M
 
 
+def born_plan(sub_c, nrows):
+    """``dnm_born_plan`` (host only): (rows of a block, blocks, bytes of the block sums) of the Born sampling passes
+    over ``nrows`` rows of the subspace."""
+    br, nb, sb = C.c_int64(), C.c_int64(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_born_plan(C.byref(sub_c), int(nrows), C.byref(br), C.byref(nb), C.byref(sb)))
+    return br.value, nb.value, int(sb.value)
+
+
+def born_scan(sums, before=0.0):
+    """``dnm_born_scan`` (host only): the serial inclusive prefix of the block sums, started from ``before``."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    out = np.empty_like(sums)
+    _lib.check(_lib.lib().dnm_born_scan(_lib.pf64(sums), sums.size, float(before), _lib.pf64(out)))
+    return out
+
+
+def born_uniforms(seed, shot0, nshots):
+    """``dnm_born_uniforms`` (host only): ``(u, flip)`` of the shots shot0 .. shot0 + nshots - 1 under ``seed``, float64
+    in [0, 1) and uint8."""
+    u, flip = np.empty(int(nshots), dtype=np.float64), np.empty(int(nshots), dtype=np.uint8)
+    _lib.check(_lib.lib().dnm_born_uniforms(int(seed) & (2 ** 64 - 1), int(shot0), int(nshots), _lib.pf64(u),
+                                            flip.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return u, flip
+
+
+def born_block_sums(x_block, sub_c, row0, nrows, before=0.0):
+    """``dnm_born_block_sums`` of the rows [row0, row0 + nrows) that the device tensor ``x_block`` holds: ``(sums,
+    scan)``, the weight of each block of ``born_plan`` rows and its inclusive prefix from ``before``."""
+    nb = born_plan(sub_c, nrows)[1]
+    sums, scan = np.empty(nb, dtype=np.float64), np.empty(nb, dtype=np.float64)
+    _lib.check(_lib.lib().dnm_born_block_sums(C.c_void_p(x_block.data_ptr()), C.byref(sub_c), int(row0), int(nrows),
+                                              float(before), _lib.pf64(sums), _lib.pf64(scan), _stream()))
+    return sums, scan
+
+
+def born_search(x_block, sub_c, row0, nrows, targets, before=0.0, final=True):
+    """``dnm_born_search``: for each of ``targets`` the global index of the row of the block that holds it, -1 where it
+    belongs to another block.  ``final``: no rows follow this block, its last row of weight takes the targets at or
+    beyond the total."""
+    targets = np.ascontiguousarray(targets, dtype=np.float64)
+    rows = np.empty(targets.size, dtype=np.int64)
+    _lib.check(_lib.lib().dnm_born_search(C.c_void_p(x_block.data_ptr()), C.byref(sub_c), int(row0), int(nrows),
+                                          float(before), int(bool(final)), targets.size, _lib.pf64(targets),
+                                          _lib.p64(rows), _stream()))
+    return rows
+
+
+def born_sample_block(x_block, sub_c, row0, nrows, seed, shot0, nshots):
+    """``dnm_born_sample``: ``(rows, flips)`` of the shots shot0 .. shot0 + nshots - 1 under ``seed`` from the whole
+    state that the device tensor ``x_block`` holds; int64 and uint8."""
+    rows, flips = np.empty(int(nshots), dtype=np.int64), np.empty(int(nshots), dtype=np.uint8)
+    _lib.check(_lib.lib().dnm_born_sample(C.c_void_p(x_block.data_ptr()), C.byref(sub_c), int(row0), int(nrows),
+                                          int(seed) & (2 ** 64 - 1), int(shot0), int(nshots), _lib.p64(rows),
+                                          flips.ctypes.data_as(C.POINTER(C.c_uint8)), _stream()))
+    return rows, flips
+
+
+BORN_SHOT_CHUNK = 1 << 20       # shots of one call: 9 MB of host buffers, 17 MB on the device
+
+
+def born_sample(vec, subspace, shots, seed):
+    """``shots`` rows drawn from |psi_i|^2 / <psi|psi> without the state leaving the device: ``(rows, flips)``, the
+    basis indices (int64) and one fair coin per shot (uint8, what an XParity state's caller uses between a
+    representative and its flip).  ``subspace`` as for ``zz_moments``.  Swizzled Full / Parity vectors are read as they
+    lie; a SpinConserve vector in the internal layout is converted to reference order first (one extra vector).  Each
+    chunk of shots makes its own pass for the block sums.  Every row is -1 when the state has no weight.  One rank only:
+    on more this raises ``NotImplementedError`` (the C ABI is block-wise, the draw over the ranks is not written)."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('Born sampling of a partitioned state')
+    x, sub_c = _reference_order(vec, subspace['data'])
+    shots = int(shots)
+    rows, flips = np.empty(shots, dtype=np.int64), np.empty(shots, dtype=np.uint8)
+    for lo in range(0, shots, BORN_SHOT_CHUNK):
+        hi = min(shots, lo + BORN_SHOT_CHUNK)
+        rows[lo:hi], flips[lo:hi] = born_sample_block(x, sub_c, vec.start, vec.rows, seed, lo, hi - lo)
+    return rows, flips
+
+
+BORN_MAX_Q = 8      # exponents of one power-sum pass (csrc/born.h)
+
+
+def power_sums_block(x_block, n, qs):
+    """``dnm_vec_power_sums`` of the ``n`` elements of the device tensor ``x_block`` for up to 8 exponents ``qs`` > 0:
+    float64 array (P_0, ..., P_{nq-1}, W, H, wmax, nnz)."""
+    qs = np.ascontiguousarray(qs, dtype=np.float64)
+    out = np.empty(qs.size + 4, dtype=np.float64)
+    _lib.check(_lib.lib().dnm_vec_power_sums(C.c_void_p(x_block.data_ptr()), int(n), qs.size, _lib.pf64(qs),
+                                             _lib.pf64(out), _stream()))
+    return out
+
+
+def power_sums(vec, qs):
+    """``(P, W, H, wmax, nnz)`` of the weights w_i = |psi_i|^2 of the state in ``vec``: P[k] = sum w^qs[k] (qs finite and
+    > 0), W = sum w, H = sum w ln w, the largest w and the number of w > 0.  The vector goes in as it lies, whatever its
+    layout (the padding of the SpinConserve internal layout is zeros); more than 8 exponents take several passes.  One
+    rank only: on more this raises ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('power sums of a partitioned state')
+    qs = [float(q) for q in qs]
+    P, rest = [], None
+    for lo in range(0, max(len(qs), 1), BORN_MAX_Q):
+        out = power_sums_block(vec.array, vec.local_size, qs[lo:lo + BORN_MAX_Q])
+        P.extend(out[:-4])
+        rest = out[-4:]
+    return np.array(P, dtype=np.float64), rest[0], rest[1], rest[2], rest[3]
+
+
 def pm_moments_plan(sub_c):
     """``dnm_pm_moments_plan`` (host only): (tile rows of 16, log2 of the panel's rows, workgroups, bytes of LDS of a
     launch, bytes of the partial tiles) of the sigma+ sigma- sweep over a state of the subspace."""

@@ -663,6 +663,97 @@ def sigmaz_correlations(state, connected=False):
     return mz, zz
 
 
+def _basis_weights_subspace(state, what):
+    """The subspace of ``state`` and whether it is an XParity one, for the passes over |psi_c|^2."""
+    from .subspaces import XParity
+    state.assert_initialized()
+    config._initialize()
+    sp = state.subspace
+    flip_sector = type(sp) is XParity
+    if not (sp.product_state_basis or flip_sector):
+        raise ValueError('%s needs a product state basis or an XParity subspace, not %r' % (what, sp))
+    return sp, flip_sector
+
+
+def sample(state, shots, seed=None):
+    """``shots`` measurements of ``state`` in the computational basis: int64 array of product states as integers (bit
+    i = spin i, as ``subspace.idx_to_state`` gives them), drawn with probability |psi_c|^2 / <psi|psi> on the device
+    (``backend.born_sample``: one pass over the state and a search per shot; the state is not copied to the host and
+    need not be normalised).  A configuration of weight zero is never returned.  ``seed`` (an integer; None draws one
+    from ``os.urandom``) fixes the shots: shot s is the same whatever ``shots`` is.
+
+    Full, Parity, SpinConserve, Explicit / Auto and XParity states on one process.  A basis vector of an XParity
+    subspace is (|c> +- |~c>) / sqrt 2, so each shot returns the representative c or its global flip ~c by a fair coin
+    of the same generator.  A state of zero norm raises ``ValueError``."""
+    from . import backend
+    sp, flip_sector = _basis_weights_subspace(state, 'sampling')
+    shots = int(shots)
+    if shots < 0:
+        raise ValueError('shots must not be negative')
+    if seed is None:
+        import os
+        seed = int.from_bytes(os.urandom(8), 'little')
+    # (an XParity descriptor is its parent's: the vector holds the parent's first dim / 2 rows)
+    rows, flips = backend.born_sample(state.vec, sp._to_c(), shots, seed)
+    if np.any(rows < 0):
+        raise ValueError('cannot sample a state of zero norm')
+    out = np.asarray(sp.idx_to_state(rows), dtype=np.int64).reshape(-1)
+    if flip_sector:
+        out = np.where(flips != 0, out ^ ((1 << sp.L) - 1), out)
+    return out
+
+
+def _power_exponents(qs):
+    """The exponents of ``qs`` that need a power sum: the finite ones other than 0 and 1."""
+    return [q for q in qs if np.isfinite(q) and q != 0 and q != 1]
+
+
+def participation_from_sums(qs, P, W, H, wmax, nnz, flip_sector=False):
+    """The participation entropies S_q, q in ``qs``, from the sums over the weights w of a state's amplitudes: ``P``
+    = sum w^q for the exponents ``_power_exponents(qs)`` in their order, ``W`` = sum w, ``H`` = sum w ln w, the largest
+    weight and the number of non-zero ones.  S_q = (ln P_q - q ln W) / (1 - q); q = 1: ln W - H / W; q = inf:
+    -ln(wmax / W); q = 0: ln nnz.  ``flip_sector``: the sums run over the representatives of an XParity state, each of
+    whose weights splits in two in the product basis -- P_q picks up 2^(1-q), H loses W ln 2, wmax halves and nnz
+    doubles (every entropy gains ln 2)."""
+    P = np.asarray(P, dtype=np.float64)
+    need = _power_exponents(qs)
+    if P.size != len(need):
+        raise ValueError('%d power sums for %d exponents' % (P.size, len(need)))
+    if flip_sector:
+        P = P * np.exp2(1.0 - np.array(need, dtype=np.float64)) if need else P
+        H, wmax, nnz = H - W * np.log(2.0), wmax / 2.0, 2.0 * nnz
+    out, k = np.empty(len(qs), dtype=np.float64), 0
+    for i, q in enumerate(qs):
+        if q == 0:
+            out[i] = np.log(nnz)
+        elif q == 1:
+            out[i] = np.log(W) - H / W
+        elif np.isinf(q):
+            out[i] = -np.log(wmax / W)
+        else:
+            out[i] = (np.log(P[k]) - q * np.log(W)) / (1.0 - q)
+            k += 1
+    return out
+
+
+def participation_entropies(state, qs=(2,)):
+    """The participation (basis Renyi) entropies S_q = ln(sum_c p_c^q) / (1 - q) of ``state`` in the product basis, p_c
+    = |psi_c|^2 / <psi|psi>: float64 array, one value per q of ``qs`` (q >= 0; q = 1 is the Shannon entropy, ``np.inf``
+    the min-entropy -ln max p, 0 the logarithm of the number of non-zero amplitudes).  One pass over the state on the
+    device for up to 8 exponents other than 0, 1 and inf (``backend.power_sums``); the state need not be normalised.
+    States on XParity subspaces count in the product basis, where each representative's weight splits in two.  One
+    process only."""
+    from . import backend
+    sp, flip_sector = _basis_weights_subspace(state, 'participation entropies')
+    qs = [float(q) for q in np.atleast_1d(np.asarray(qs, dtype=np.float64))]
+    if any(np.isnan(q) or q < 0 for q in qs):
+        raise ValueError('participation entropies are defined for q >= 0')
+    P, W, H, wmax, nnz = backend.power_sums(state.vec, _power_exponents(qs))
+    if not W > 0:
+        raise ValueError('participation entropies of a state of zero norm')
+    return participation_from_sums(qs, P, W, H, wmax, nnz, flip_sector)
+
+
 def _pm_subspace(state, what):
     from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
     sp = state.subspace

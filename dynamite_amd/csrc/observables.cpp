@@ -1,8 +1,10 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
 // density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap, three-site rotation
-// (chirality) and two-spin Pauli moments -- the Gram matrix of many vectors, which runs on the same panel scheme, and
-// the site permutations of a state (two plain gather kernels, no panel).  They share the cached scratch of the partial
+// (chirality) and two-spin Pauli moments -- the Gram matrix of many vectors, which runs on the same panel scheme, the
+// site permutations of a state (two plain gather kernels, no panel), and Born sampling with the power sums of the
+// participation entropies (streaming passes over |x_i|^2, no panel).  They share the cached scratch of the partial
 // tiles.
+#include "born.h"
 #include "gram_tile.h"
 #include "mat.h"
 #include "pm_rank.h"
@@ -239,14 +241,15 @@ int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size,
 }
 
 // ---- first and second sigma-z moments -----------------------------------------------------------------------------
-// what the plan and the call check alike: the descriptor, the layout and the rows
-static int zz_check(const dnm_subspace *sub, int64_t row0, int64_t nrows, SubView *v) {
+// what the plans and the calls of the passes over a block of rows (`what`: sigma-z moments, Born sampling) check alike:
+// the descriptor, the layout and the rows
+static int rows_check(const char *what, const dnm_subspace *sub, int64_t row0, int64_t nrows, SubView *v) {
   DNM_CHECK(sub, "null argument");
   DNM_TRY(view_from_c(sub, v));
-  DNM_CHECK(v->sc3 == 0, "sigma-z moments read a SpinConserve state in reference order (vec_swizzle %d given: "
-            "dnm_vec_layout_copy converts)", v->sc3);
-  DNM_CHECK(sub->site_perm == nullptr, "sigma-z moments take no relabelled subspace (site_perm given): hand over the "
-            "state in reference order with a descriptor without it");
+  DNM_CHECK(v->sc3 == 0, "%s read a SpinConserve state in reference order (vec_swizzle %d given: "
+            "dnm_vec_layout_copy converts)", what, v->sc3);
+  DNM_CHECK(sub->site_perm == nullptr, "%s take no relabelled subspace (site_perm given): hand over the "
+            "state in reference order with a descriptor without it", what);
   const int64_t dim = sub_dim(*v);
   DNM_CHECK(nrows >= 0 && row0 >= 0 && nrows <= dim && row0 <= dim - nrows,
             "rows [%lld, %lld + %lld) of a subspace of dimension %lld", (long long)row0, (long long)row0,
@@ -260,7 +263,7 @@ static int zz_check(const dnm_subspace *sub, int64_t row0, int64_t nrows, SubVie
 int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
                         size_t *scratch_bytes) {
   SubView v{};
-  DNM_TRY(zz_check(sub, 0, nrows, &v));
+  DNM_TRY(rows_check("sigma-z moments", sub, 0, nrows, &v));
   int nb, nwg;
   int64_t per_wg;
   size_t bytes;
@@ -272,7 +275,7 @@ int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, 
 int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream) {
   DNM_CHECK(out && (x || nrows == 0), "null argument");
   SubView v{};
-  DNM_TRY(zz_check(sub, row0, nrows, &v));
+  DNM_TRY(rows_check("sigma-z moments", sub, row0, nrows, &v));
   int nb, nwg;
   int64_t per_wg;
   size_t pbytes;
@@ -288,6 +291,153 @@ int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t
   DNM_TRY(launch_zz_moments(x, s.dev, row0, nrows, scratch, m_dev, S(stream)));
   // (synchronises: the subspace tables are released on return)
   return dnm_memcpy_d2h(out, m_dev, D * D * sizeof(double), stream);
+}
+
+// ---- Born sampling and the power sums of the participation entropies (born.h, born_kernels.hip) -------------------
+int dnm_born_plan(const dnm_subspace *sub, int64_t nrows, int64_t *block_rows, int64_t *nblocks, size_t *scratch_bytes) {
+  SubView v{};
+  DNM_TRY(rows_check("Born sampling passes", sub, 0, nrows, &v));
+  int64_t nb, nwg;
+  size_t bytes;
+  born_plan(nrows, &nb, &nwg, &bytes);
+  if (block_rows) *block_rows = BORN_BLOCK_ROWS;
+  if (nblocks) *nblocks = nb;
+  if (scratch_bytes) *scratch_bytes = bytes;
+  return 0;
+}
+
+int dnm_born_scan(const double *sums_host, int64_t n, double before, double *scan_host) {
+  DNM_CHECK(n >= 0 && (n == 0 || (sums_host && scan_host)), "null argument");
+  born_scan(sums_host, n, before, scan_host);
+  return 0;
+}
+
+int dnm_born_uniforms(uint64_t seed, int64_t shot0, int64_t nshots, double *u_host, uint8_t *flip_host) {
+  DNM_CHECK(nshots >= 0 && (u_host || nshots == 0), "null argument");
+  for (int64_t s = 0; s < nshots; ++s) {
+    uint8_t flip;
+    u_host[s] = born_uniform((uint64_t)(shot0 + s), seed, &flip);
+    if (flip_host) flip_host[s] = flip;
+  }
+  return 0;
+}
+
+namespace {
+// the scanned block sums of a block of rows on the device, with `extra` bytes of scratch behind them for the shots
+struct BornScan {
+  std::vector<double> host;      // the block sums, then their scan
+  DevBuf big;
+  double *scan_dev = nullptr;
+  char *extra_dev = nullptr;
+  int64_t nblocks = 0, last = -1;      // last: the last block that carries weight
+  double total = 0.0;                  // the last scan value: `before` + the weight of the rows
+};
+}  // namespace
+
+// sums_out (host, may be null) gets the block sums.  Synchronises the stream.  for_search: the scan goes back to the
+// device; bs->host backs that upload, which is still in flight on return, and lives until the caller's own
+// synchronisation.
+static int born_scan_rows(const void *x, const SubView &v, int64_t nrows, double before, size_t extra, double *sums_out,
+                          bool for_search, BornScan *bs, void *stream) {
+  int64_t nwg;
+  size_t bytes;
+  born_plan(nrows, &bs->nblocks, &nwg, &bytes);
+  void *scratch = nullptr;
+  DNM_TRY(rdm_scratch(bytes + extra + 8, &bs->big, &scratch, "Born sampling", (long long)bs->nblocks, 32, 1));
+  bs->scan_dev = (double *)scratch;
+  bs->extra_dev = (char *)scratch + bytes;
+  bs->host.resize((size_t)bs->nblocks);
+  bs->total = before;
+  if (bs->nblocks == 0) return 0;
+  DNM_TRY(launch_born_block_sums(x, v.swz, nrows, bs->scan_dev, S(stream)));
+  DNM_TRY(dnm_memcpy_d2h(bs->host.data(), bs->scan_dev, bytes, stream));
+  if (sums_out) memcpy(sums_out, bs->host.data(), bytes);
+  bs->last = born_last_weight(bs->host.data(), bs->nblocks);
+  bs->total = born_scan(bs->host.data(), bs->nblocks, before, bs->host.data());
+  if (for_search) DNM_HIP(hipMemcpyAsync(bs->scan_dev, bs->host.data(), bytes, hipMemcpyHostToDevice, S(stream)));
+  return 0;
+}
+
+int dnm_born_block_sums(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double before,
+                        double *sums_host, double *scan_host, void *stream) {
+  DNM_CHECK(x || nrows == 0, "null argument");
+  DNM_CHECK(before >= 0.0, "the weight in front of a block cannot be negative");
+  SubView v{};
+  DNM_TRY(rows_check("Born sampling passes", sub, row0, nrows, &v));
+  BornScan bs;
+  DNM_TRY(born_scan_rows(x, v, nrows, before, 0, sums_host, false, &bs, stream));
+  if (scan_host && bs.nblocks) memcpy(scan_host, bs.host.data(), (size_t)bs.nblocks * sizeof(double));
+  return 0;
+}
+
+int dnm_born_search(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double before, int final_block,
+                    int64_t nshots, const double *targets_host, int64_t *rows_host, void *stream) {
+  DNM_CHECK((x || nrows == 0) && nshots >= 0 && (nshots == 0 || (targets_host && rows_host)), "null argument");
+  DNM_CHECK(before >= 0.0, "the weight in front of a block cannot be negative");
+  SubView v{};
+  DNM_TRY(rows_check("Born sampling passes", sub, row0, nrows, &v));
+  const size_t sbytes = (size_t)nshots * 8;
+  BornScan bs;
+  DNM_TRY(born_scan_rows(x, v, nrows, before, 2 * sbytes, nullptr, true, &bs, stream));
+  double *t_dev = (double *)bs.extra_dev;
+  int64_t *r_dev = (int64_t *)(bs.extra_dev + sbytes);
+  if (nshots) DNM_HIP(hipMemcpyAsync(t_dev, targets_host, sbytes, hipMemcpyHostToDevice, S(stream)));
+  BornSearch p{};
+  p.row0 = row0;
+  p.nrows = nrows;
+  p.nblocks = bs.nblocks;
+  p.nshots = nshots;
+  p.before = before;
+  p.clamp_block = final_block ? bs.last : -1;
+  p.targets_dev = t_dev;
+  DNM_TRY(launch_born_search(x, v.swz, bs.scan_dev, p, r_dev, nullptr, S(stream)));
+  // (synchronises: the host scan and `big` are released on return)
+  return dnm_memcpy_d2h(rows_host, r_dev, sbytes, stream);
+}
+
+int dnm_born_sample(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, uint64_t seed, int64_t shot0,
+                    int64_t nshots, int64_t *rows_host, uint8_t *flip_host, void *stream) {
+  DNM_CHECK((x || nrows == 0) && nshots >= 0 && shot0 >= 0 && (nshots == 0 || rows_host), "null argument");
+  SubView v{};
+  DNM_TRY(rows_check("Born sampling passes", sub, row0, nrows, &v));
+  const size_t sbytes = (size_t)nshots * 8;
+  BornScan bs;
+  DNM_TRY(born_scan_rows(x, v, nrows, 0.0, sbytes + (size_t)nshots, nullptr, true, &bs, stream));
+  int64_t *r_dev = (int64_t *)bs.extra_dev;
+  uint8_t *f_dev = (uint8_t *)(bs.extra_dev + sbytes);
+  BornSearch p{};
+  p.row0 = row0;
+  p.nrows = nrows;
+  p.nblocks = bs.nblocks;
+  p.nshots = nshots;
+  p.clamp_block = bs.last;
+  p.seed = seed;
+  p.shot0 = shot0;
+  p.total = bs.total;
+  DNM_TRY(launch_born_search(x, v.swz, bs.scan_dev, p, r_dev, f_dev, S(stream)));
+  if (flip_host && nshots) DNM_HIP(hipMemcpyAsync(flip_host, f_dev, (size_t)nshots, hipMemcpyDeviceToHost, S(stream)));
+  // (synchronises: the host scan and `big` are released on return)
+  return dnm_memcpy_d2h(rows_host, r_dev, sbytes, stream);
+}
+
+int dnm_vec_power_sums(const void *x, int64_t n, int nq, const double *q_host, double *out_host, void *stream) {
+  DNM_CHECK((x || n == 0) && n >= 0 && out_host && nq >= 0 && (nq == 0 || q_host), "null argument");
+  DNM_CHECK(nq <= BORN_MAX_Q, "%d exponents in one pass: at most %d", nq, BORN_MAX_Q);
+  for (int k = 0; k < nq; ++k)
+    DNM_CHECK(q_host[k] > 0.0 && q_host[k] < 1e300, "exponent %g: the power sums take finite q > 0", q_host[k]);
+  const int64_t nwg = born_power_workgroups(n);
+  const size_t bytes = (size_t)nwg * BORN_NSUMS * sizeof(double);
+  DevBuf big;
+  void *scratch = nullptr;
+  DNM_TRY(rdm_scratch(bytes, &big, &scratch, "power sums", (long long)nwg, 1, 1));
+  DNM_TRY(launch_born_power_sums(x, n, nq, q_host, (double *)scratch, S(stream)));
+  std::vector<double> part((size_t)nwg * BORN_NSUMS);
+  DNM_TRY(dnm_memcpy_d2h(part.data(), scratch, bytes, stream));
+  double all[BORN_NSUMS];
+  born_power_reduce(part.data(), nwg, all);
+  for (int k = 0; k < nq; ++k) out_host[k] = all[k];
+  for (int c = 0; c < 4; ++c) out_host[nq + c] = all[BORN_MAX_Q + c];
+  return 0;
 }
 
 // ---- sigma+ sigma- moments ----------------------------------------------------------------------------------------

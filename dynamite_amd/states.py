@@ -264,6 +264,16 @@ class State:
         from . import computations
         return computations.sigmaz_correlations(self, connected=connected)
 
+    def sample(self, shots, seed=None):
+        """``shots`` measurements in the computational basis, drawn on the device -> computations.sample."""
+        from . import computations
+        return computations.sample(self, shots, seed=seed)
+
+    def participation_entropies(self, qs=(2,)):
+        """The participation (basis Renyi) entropies S_q in one pass -> computations.participation_entropies."""
+        from . import computations
+        return computations.participation_entropies(self, qs=qs)
+
     def sigma_pm_correlations(self):
         """``pm[i, j]`` = <sigma_plus(i) sigma_minus(j)> for every pair in one pass -> computations.sigma_pm_correlations."""
         from . import computations

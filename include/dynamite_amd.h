@@ -216,6 +216,57 @@ int dnm_rdm_sector_blocks(const void *x, const dnm_subspace *sub, int keep_size,
 int dnm_zz_moments_plan(const dnm_subspace *sub, int64_t nrows, int *tile_rows, int *nworkgroups,
                         size_t *scratch_bytes);
 int dnm_zz_moments(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double *out, void *stream);
+/* Measurement in the computational basis: rows drawn from w_i = |x_i|^2 / <x|x> without the vector leaving the device
+ * (no counterpart in the reference, whose users take State.to_numpy() and numpy.random.choice on the host).  x (device)
+ * holds the nrows amplitudes of the rows [row0, row0 + nrows) of sub, as for dnm_zz_moments: vec_swizzle 0 is index
+ * order, the XOR swizzle of Full / Parity is read as it lies and acts on the block's own positions, the SpinConserve
+ * internal layout and a non-null site_perm are refused.  Rows are counted in index order and returned as indices,
+ * never positions; the descriptor serves the checks alone, so an XParity half goes in under its parent's descriptor
+ * with nrows = dim / 2.
+ * The rows are cut into blocks of block_rows rows (a power of two; the last block may be ragged).  One pass gives the
+ * block sums B_b of the weights; their inclusive prefix S_b, started from `before` (the weight of all rows in front of
+ * this block: earlier ranks, earlier pieces), is a serial sum and therefore non-decreasing.  A target t >= 0 goes to
+ * the smallest b with S_b > t and in it to the smallest row whose in-block prefix (serial chunks of 16 rows on serially
+ * summed offsets: non-decreasing too, and flat across rows of weight zero) exceeds t - S_{b-1}; where rounding leaves
+ * no such row, to the block's last row of non-zero weight.  A row of weight exactly zero is never returned.  All sums
+ * have fixed shapes and use no atomics: two calls return the same bits, on any device.  Cost: one pass over the rows
+ * and one block of rows per shot; scratch: the block sums, and 16 bytes per shot.
+ * dnm_born_plan (host only, no device needed): block_rows, nblocks = ceil(nrows / block_rows) and the bytes of the
+ * block sums -- functions of nrows alone; any output may be null.
+ * dnm_born_scan (host only): the scan as the calls below make it, scan[b] = before + sums[0] + ... + sums[b] (in place
+ * allowed).  dnm_born_uniforms (host only): u and the flip bit of the shots shot0 .. shot0 + nshots - 1 of
+ * dnm_born_sample (flip_host may be null).
+ * dnm_born_block_sums: the block sums and their scan from `before` to the HOST (nblocks doubles each, either may be
+ * null): a caller of a partitioned state learns each block's weight from it.
+ * dnm_born_search: rows_host[s] (HOST) = row0 + the local row of targets_host[s] (HOST) for the targets in [before,
+ * before + the weight of these rows), -1 for every other target -- they belong to other blocks.  final_block != 0 says
+ * that no rows follow these: targets at or beyond the total (u W can round up to W) then go to the last row of non-zero
+ * weight (-1 when these rows carry no weight at all).
+ * dnm_born_sample: the whole state in one block (before = 0, final).  Shot s draws Philox-4x32-10 with the counter
+ * words (lo32(shot0 + s), hi32(shot0 + s), 0x13198A2E, 0x03707344) under the key seed -- the constant words differ from
+ * those of dnm_vec_set_random, whose bits set |x_i| -- and output words c0..c3: u = (((c0 << 32) | c1) >> 11) 2^-53,
+ * target t = u W in one rounding with W the last scan value, flip_host[s] (may be null) = c2 & 1, the coin an XParity
+ * state's caller uses between a representative and its global flip.  Chunks of shots (shot0) return what one call
+ * returns.  Every row is -1 when the state has no weight.
+ * These calls synchronise the stream like dnm_vec_dot; scratch comes from the library's workspace
+ * (dnm_release_workspace). */
+int dnm_born_plan(const dnm_subspace *sub, int64_t nrows, int64_t *block_rows, int64_t *nblocks, size_t *scratch_bytes);
+int dnm_born_scan(const double *sums_host, int64_t n, double before, double *scan_host);
+int dnm_born_uniforms(uint64_t seed, int64_t shot0, int64_t nshots, double *u_host, uint8_t *flip_host);
+int dnm_born_block_sums(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double before,
+                        double *sums_host, double *scan_host, void *stream);
+int dnm_born_search(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, double before, int final_block,
+                    int64_t nshots, const double *targets_host, int64_t *rows_host, void *stream);
+int dnm_born_sample(const void *x, const dnm_subspace *sub, int64_t row0, int64_t nrows, uint64_t seed, int64_t shot0,
+                    int64_t nshots, int64_t *rows_host, uint8_t *flip_host, void *stream);
+/* The sums behind the participation (basis Renyi) entropies of a vector of n elements in one pass, w_i = |x_i|^2:
+ * out (HOST, nq + 4 doubles) = P_0 .. P_{nq-1}, W, H, wmax, nnz with P_k = sum w^q_k for the nq <= 8 exponents q_host
+ * (finite, > 0), W = sum w, H = sum of w ln w over the w > 0, wmax = max w and nnz = the number of w > 0.  Exponents 2,
+ * 3 and 4 are computed by multiplication (exact on integer weights), every other one by pow.  The order of the elements
+ * does not matter: any layout whose padding is zeros goes in as it lies, the SpinConserve internal layout included
+ * (n = dnm_vec_layout_size).  Fixed reduction shapes, no atomics; the workgroups are a function of n alone.
+ * Synchronises the stream. */
+int dnm_vec_power_sums(const void *x, int64_t n, int nq, const double *q_host, double *out_host, void *stream);
 /* Every <sigma+_i sigma-_j> of a state in one pass over it -- the transverse part <sigmax_i sigmax_j + sigmay_i sigmay_j>
  * of the spin correlations, where the call above gives the sigmaz part (no counterpart in the reference, whose users
  * call Operator.expectation once per pair).  sigma_minus(j) = sigmax_j - i sigmay_j sets bit j of a configuration with
