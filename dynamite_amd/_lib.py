@@ -187,6 +187,7 @@ SIGNATURES = {
     "dnm_mat_window_split": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "dnm_mat_mult_local_part": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "dnm_mat_local_part_bits": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dnm_mat_local_part_agree": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
     "dnm_mat_mult_window_local": (C.c_int, [vp, vp, vp, vp]),
     "dnm_mat_mult_window_remote": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp]),
     "dnm_mat_window_local_rows": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int), vp]),

@@ -1117,7 +1117,10 @@ class ShellMat:
         sub = self.TR_SUB
         logsub = sub.bit_length() - 1
         swz = int(left_c.vec_swizzle)
+        agree = C.c_int()        # (a plan of several passes: range s of sub is the same amplitudes in each of them)
+        _lib.check(_lib.lib().dnm_mat_local_part_agree(hs[1], sub, C.byref(agree)))
         self._tr_pipe = (knob('DNM_TRANSPOSE_PIPE', '1') != '0' and top.value == f - 1 and gathers.value == 0
+                         and agree.value == 1
                          and cnt % sub == 0 and n - int(knob('DNM_TILE_BITS', '12')) >= logsub     # whole tiles per range
                          and (swz == 0 or 2 * swz - 4 <= f - logsub))      # parts keep their order in the swizzled layout
 

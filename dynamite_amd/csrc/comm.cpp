@@ -412,13 +412,14 @@ int setup_transposed(dnm_comm *c, dnm_mat *A, TransposeState &T) {
   T.nb = 1 << (T.n - T.f - T.p);
   // sub-piece pipelining of the second part: its ranges of workgroups must be the top bits inside a piece and must
   // not read outside themselves (backend.ShellMat.set_transposed: the same conditions)
-  int top = -1, gathers = 0;
+  int top = -1, gathers = 0, agree = 0;
   DNM_TRY(dnm_mat_local_part_bits(A->tr_hi, &top, &gathers));
+  DNM_TRY(dnm_mat_local_part_agree(A->tr_hi, TR_SUB, &agree));      // (several passes: the same ranges in each)
   int logsub = 0;
   while ((1 << logsub) < TR_SUB) ++logsub;
   const int swz = A->right.host.swz;
   const char *pk = knob("DNM_TRANSPOSE_PIPE");
-  T.pipe = !(pk && pk[0] == '0') && top == T.f - 1 && gathers == 0 && T.cnt % TR_SUB == 0 &&
+  T.pipe = !(pk && pk[0] == '0') && top == T.f - 1 && gathers == 0 && agree == 1 && T.cnt % TR_SUB == 0 &&
            T.n - A->tr_hi->plan.cfg.B >= logsub && (swz == 0 || 2 * swz - 4 <= T.f - logsub);
   T.sub = T.pipe ? TR_SUB : ((T.cnt % TR_SUB == 0 && T.cnt / TR_SUB >= 1024) ? TR_SUB : 1);
   T.part = T.cnt / T.sub;

@@ -173,6 +173,29 @@ static int sweep_column_ranges(dnm_mat *A, DevBuf *buf, ColMark mark, void *stre
                           nullptr, nullptr, nullptr, (int64_t *)buf->p, S(stream), mark);
 }
 
+// A later pass adds to what the passes before it wrote of the SAME call of dnm_mat_mult_local_part: range `part` has to
+// be the same amplitudes in every pass, i.e. the top log2(nparts) block-id bits of every pass are the same index bits in
+// the same order.  (Two tile-only passes that agree on their highest free bit need not agree on the next one: the window
+// tile of the second holds it, and its workgroups split along a lower bit -- four ranges then gave another y than the
+// whole launch.)  Returns the first pass whose ranges differ from those of pass 0, -1 if none does.
+static int part_ranges_agree(const dnm_mat *A, int nparts) {
+  if (A->local_passes.size() < 2 || nparts < 2) return -1;
+  int logp = 0;
+  while ((1 << logp) < nparts) ++logp;
+  std::vector<int> first;
+  for (size_t i = 0; i < A->local_passes.size(); ++i) {
+    const DevPass &d = A->local_passes[i]->whole.desc;
+    const int nbb = A->local_passes[i]->n_eff - d.tile_bits;
+    std::vector<int> pos;
+    for (int b = std::max(0, nbb - logp); b < nbb; ++b)
+      for (int j = 0; j < d.nbseg; ++j)
+        if (b >= d.bseg_off[j] && b < d.bseg_off[j] + d.bseg_len[j]) pos.push_back(d.bseg_pos[j] + b - d.bseg_off[j]);
+    if (i == 0) first = pos;
+    else if (pos != first) return (int)i;
+  }
+  return -1;
+}
+
 extern "C" {
 
 int dnm_mat_mult_local(dnm_mat *A, const void *x, void *y, void *stream) {
@@ -191,6 +214,9 @@ int dnm_mat_mult_local_part(dnm_mat *A, const void *x, void *y, int part, int np
   DNM_CHECK(A && x && y && x != y && !A->host_only, "bad argument");
   DNM_CHECK(A->route == Route::Tiled, "only the tiled hypercube passes run over a range of their workgroups");
   DNM_CHECK(nparts >= 1 && (nparts & (nparts - 1)) == 0 && part >= 0 && part < nparts, "bad range %d of %d", part, nparts);
+  DNM_CHECK(part_ranges_agree(A, nparts) < 0,
+            "the %d ranges of pass %d of this plan are not the amplitudes of the ranges of its first pass", nparts,
+            part_ranges_agree(A, nparts));
   for (auto &p : A->local_passes) {
     const unsigned grid = 1u << (p->n_eff - p->whole.desc.tile_bits);
     DNM_CHECK((unsigned)nparts <= grid, "more ranges than workgroups");
@@ -199,6 +225,14 @@ int dnm_mat_mult_local_part(dnm_mat *A, const void *x, void *y, int part, int np
     c.nparts = (unsigned)nparts;
     DNM_TRY(launch_pass(A, *p, c, x, y, nullptr, S(stream)));
   }
+  return 0;
+}
+
+// 1 if range `part` of nparts is the same amplitudes in every rank-local pass (always on a plan of one pass): what
+// dnm_mat_mult_local_part needs, for callers that decide beforehand whether to run by ranges
+int dnm_mat_local_part_agree(const dnm_mat *A, int nparts, int *agree) {
+  DNM_CHECK(A && agree && nparts >= 1 && (nparts & (nparts - 1)) == 0, "bad argument");
+  *agree = part_ranges_agree(A, nparts) < 0 ? 1 : 0;
   return 0;
 }
 

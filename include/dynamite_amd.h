@@ -593,10 +593,15 @@ int dnm_mat_window_split(const dnm_mat *A, int *supported);
 /* Tiled Full / Parity operators: the rank-local passes over one of `nparts` (a power of two) equal ranges of their
  * workgroups.  dnm_mat_local_part_bits tells what a range is: *top_free_bit = the highest index bit outside every tile
  * (range `part` covers the amplitudes whose log2(nparts) index bits ending there equal `part`), *gathers = records
- * that read outside the tile (0: a range reads and writes its own amplitudes only).  The transposed exchange runs its
- * layout-B pass sub-piece by sub-piece this way. */
+ * that read outside the tile (0: a range reads and writes its own amplitudes only).  That description of a range holds
+ * where the log2(nparts) index bits ending at *top_free_bit lie outside every pass's tile; dnm_mat_mult_local_part
+ * refuses a plan of several passes whose ranges are not the same amplitudes in every pass (a later pass adds to what the
+ * earlier ones wrote in the same call).  The transposed exchange runs its layout-B pass sub-piece by sub-piece this way. */
 int dnm_mat_mult_local_part(dnm_mat *A, const void *x, void *y, int part, int nparts, void *stream);
 int dnm_mat_local_part_bits(const dnm_mat *A, int *top_free_bit, int *gathers);
+/* *agree = 1 if range `part` of nparts is the same amplitudes in every rank-local pass (always so on a plan of one pass),
+ * 0 if dnm_mat_mult_local_part would refuse: for callers that decide beforehand whether to run by ranges */
+int dnm_mat_local_part_agree(const dnm_mat *A, int nparts, int *agree);
 int dnm_mat_mult_window_local(dnm_mat *A, const void *x_local, void *y_local, void *stream);
 int dnm_mat_mult_window_remote(dnm_mat *A, const void *x_window, int64_t win_start, int64_t win_len, void *y_local,
                                void *stream);
