@@ -213,6 +213,7 @@ SIGNATURES = {
     "dnm_mat_export_diag_tables": (C.c_int, [vp, C.c_int, C.c_int, f64p, C.c_int64, i64p, f64p, C.c_int64, i64p,
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "dnm_mat_export_sc3": (C.c_int, [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dnm_mat_export_sc_block": (C.c_int, [vp, i64p, C.POINTER(C.c_uint32), C.c_int64]),
     "dnm_mat_ownership": (C.c_int, [vp, i64p, i64p]),
     "dnm_mat_column_window": (C.c_int, [vp, i64p, i64p, vp]),
     "dnm_mat_column_chunks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), C.c_int64, vp]),

@@ -1129,6 +1129,27 @@ int dnm_mat_export_sc3(const dnm_mat *A, const char *name, void *out, size_t max
   return 0;
 }
 
+// What the block form of a SpinConserve pair in reference order launches (setup_sc_block): fields[0..5] = low bits per
+// block (0: the handle does not run the block form, everything else is 0 then), first and last high part, swizzle,
+// entries of the block order, workgroups of a launch (sc_block_grid); perm_out != null: the block order itself
+// (0xffffffff: a workgroup without a block), copied from the device.  Reads only.
+int dnm_mat_export_sc_block(const dnm_mat *A, int64_t *fields, uint32_t *perm_out, int64_t max_perm) {
+  DNM_CHECK(A && fields, "null argument");
+  for (int i = 0; i < 6; ++i) fields[i] = 0;
+  if (A->host_only || A->route != Route::ScBlock) return 0;
+  const ScBlock &b = A->scblock;
+  fields[0] = b.lb;
+  fields[1] = b.h_first;
+  fields[2] = b.h_last;
+  fields[3] = b.swizzle;
+  fields[4] = b.perm ? b.nperm : 0;
+  fields[5] = sc_block_grid(b);
+  if (!perm_out || !b.perm) return 0;
+  DNM_CHECK(max_perm >= b.nperm, "the block order has %lld entries, the buffer %lld", (long long)b.nperm,
+            (long long)max_perm);
+  return dnm_memcpy_d2h(perm_out, b.perm, (size_t)b.nperm * sizeof(uint32_t), nullptr);
+}
+
 int dnm_mat_plan_counts(const dnm_mat *A, int *n_local_passes, int *n_remote_passes, int *tiled,
                         int *B, int *logR, int *n_loc) {
   DNM_CHECK(A, "null matrix");

@@ -535,6 +535,15 @@ int dnm_mat_export_diag_tables(const dnm_mat *A, int remote, int idx, double *db
  * size alone */
 int dnm_mat_export_sc3(const dnm_mat *A, const char *name, void *out, size_t max_bytes, size_t *nbytes);
 
+/* What the block form of a SpinConserve pair in reference order launches (read-only; diagnostics and tests).  fields[6]:
+ * the low bits per block (10 or 13; 0 on every handle that does not run the block form -- the other fields are 0 then),
+ * the first and the last high part state >> lb of the handle's rows (the first rounded down to a multiple of 512 under
+ * the swizzle), swizzle (1: workgroup b owns high part ((b >> 9) << 9) | ((b & 7) << 6) | ((b >> 3) & 63) counted from
+ * the first; the grid is the span rounded up to a multiple of 512), the number of entries of the block order (0: none), and the workgroups of one launch.  perm_out (HOST, may be null; at
+ * least fields[4] entries): the block order, workgroup -> high part counted from the first, 0xffffffff for a workgroup
+ * without a block. */
+int dnm_mat_export_sc_block(const dnm_mat *A, int64_t *fields, uint32_t *perm_out, int64_t max_perm);
+
 /* --- partitioned multiply: replaces the VecScatterCreateToAll all-gather of
  * bcuda_template_2.cu:161-171 with an XOR-partner exchange. ---------------- */
 /* One block transfer of the exchange: `count` amplitudes starting at `offset`
