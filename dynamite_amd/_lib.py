@@ -167,6 +167,10 @@ SIGNATURES = {
     "dnm_perm_apply": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, C.c_int,
                                  vp]),
     "dnm_perm_dots": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, vp]),
+    "dnm_site_ops_plan": (C.c_int, [C.POINTER(Subspace), f64p, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int8), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "dnm_site_ops_apply": (C.c_int, [vp, vp, C.POINTER(Subspace), f64p, vp]),
+    "dnm_mat_expm_diagonal": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp]),
     "dnm_vec_gram_plan": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "dnm_vec_gram": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int64, f64p, vp]),

@@ -2314,6 +2314,65 @@ def vec_gram(vecs):
     return vec_gram_ptrs([v.array.data_ptr() for v in same], first.local_size)
 
 
+def _site_mats_c(mats, L):
+    mats = np.ascontiguousarray(mats, dtype=np.complex128)
+    if mats.shape != (int(L), 2, 2):
+        raise ValueError('site operators of %d spins are an array of shape (%d, 2, 2), not %r'
+                         % (int(L), int(L), mats.shape))
+    return mats, mats.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))
+
+
+def site_ops_plan(sub_c, mats):
+    """``dnm_site_ops_plan`` (host only): (tile_bits, passes, site_pass -- int8 array (L,): -1 identity, -2 diagonal,
+    else the pass of a general site -- workgroups of a pass, bytes of LDS of a launch) of the product of the
+    single-site operators ``mats`` (complex array (L, 2, 2), ``mats[j]`` on spin j) over a Full-space state."""
+    mats, mp = _site_mats_c(mats, sub_c.L)
+    tb, npass, nw, lb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    site_pass = np.empty(int(sub_c.L), dtype=np.int8)
+    _lib.check(_lib.lib().dnm_site_ops_plan(C.byref(sub_c), mp, C.byref(tb), C.byref(npass),
+                                            site_pass.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(nw), C.byref(lb)))
+    return tb.value, npass.value, site_pass, nw.value, int(lb.value)
+
+
+def site_ops_apply(vec, subspace, mats, result):
+    """``result`` = (x)_j mats[j] ``vec``: the product of the single-site operators ``mats`` (complex array (L, 2, 2),
+    ``mats[j]`` any 2 x 2 matrix on spin j = index bit j) on a Full-space state, result(c') = sum_c prod_j
+    mats[j][c'_j][c_j] vec(c), in ceil(general sites above bit 3 / (tile_bits - 4)) streaming passes
+    (``dnm_site_ops_apply``).  ``subspace`` is the descriptor of the Full subspace of the vectors; swizzled vectors are
+    read and written as they lie.  ``result`` may be ``vec``: the pass then runs in place.  On more than one rank this
+    raises ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('site operators on a partitioned state: the partner amplitudes of a rank\'s rows lie '
+                                  'on other ranks')
+    sub_c = subspace['data']
+    mats, mp = _site_mats_c(mats, sub_c.L)
+    # (refused descriptors and matrices never get as far as a vector)
+    _lib.check(_lib.lib().dnm_site_ops_plan(C.byref(sub_c), mp, None, None, None, None, None))
+    if result.size != vec.size or vec.size != 1 << int(sub_c.L):
+        raise ValueError('site operators: a state of %d and a result of %d elements on %d spins'
+                         % (vec.size, result.size, int(sub_c.L)))
+    if vec.swz != int(sub_c.vec_swizzle) or result.swz != vec.swz:
+        raise ValueError('vectors of different layouts (%r, %r; the descriptor says %d)'
+                         % (vec.layout, result.layout, int(sub_c.vec_swizzle)))
+    if not (vec.array.is_cuda and result.array.is_cuda):
+        raise ValueError('site operators: the vectors must live on the device')
+    _lib.check(_lib.lib().dnm_site_ops_apply(vec.ptr, result.ptr, C.byref(sub_c), mp, _stream()))
+    return result
+
+
+def expm_diagonal(mat, x, y, s):
+    """``y`` = exp(``s`` D) ``x`` for the diagonal operator D behind the handle ``mat`` (a ``ShellMat`` whose every mask
+    is zero) and a complex ``s``, element by element in one pass (``dnm_mat_expm_diagonal``); ``x`` and ``y`` are
+    vectors in the layout the handle multiplies in, and may be the same.  An amplitude that is exactly zero stays
+    zero."""
+    config._initialize()
+    mat.check_layout(x, y)
+    s = complex(s)
+    _lib.check(_lib.lib().dnm_mat_expm_diagonal(mat.handle, x.ptr, y.ptr, s.real, s.imag, _stream()))
+    return y
+
+
 def precompute_diagonal(mat):
     """Mirror of ``bpetsc.precompute_diagonal`` (bpetsc.pyx:141-147)."""
     mat.precompute_diagonal()

@@ -152,8 +152,10 @@ def evolve(H, state, t, result=None, tol=None, ncv=None, algo=None, max_its=None
         result = State(L=H.L, subspace=state.subspace)
     elif state.subspace != result.subspace:
         raise ValueError('input and result states are on different subspaces.')
-    if algo not in (None, 'expokit', 'krylov', 'chebyshev'):
-        raise ValueError("algo must be 'expokit', 'krylov' or 'chebyshev'")
+    if algo not in (None, 'expokit', 'krylov', 'chebyshev', 'exact'):
+        raise ValueError("algo must be 'expokit', 'krylov', 'chebyshev' or 'exact'")
+    if algo == 'exact':
+        return _evolve_exact(H, state, t, result)
     if t == 0.0:
         state.copy(result)
         return result
@@ -261,6 +263,101 @@ def _evolve_chebyshev(H, state, t, result, tol):
         raise ConvergenceError('solver failed to converge.')
     if side is not None:
         side.finish()
+    result.set_initialized()
+    return result
+
+
+def product_operator_fields(H):
+    """Whether the operator ``H`` is one that ``evolve(algo='exact')`` serves, from its terms on the host:
+    ``(kind, a, c0)`` with ``kind`` = ``'diagonal'`` (every mask is 0: a function of the sigma-z alone),
+    ``'single-site'`` (a sum over sites of h_j = a_x sigmax_j + a_y sigmay_j + a_z sigmaz_j plus a constant: every mask
+    is 0 or one bit, every sign is 0 or one bit, the mask's bit where the mask is set) or None (anything else).  For
+    ``'single-site'`` ``a`` is the complex array (L, 3) of the fields (a_x, a_y, a_z) and ``c0`` the constant; a
+    diagonal operator is ``'diagonal'`` even where it is a sum of sigma-z fields, and then ``a`` is None."""
+    H.establish_L()
+    H.reduce_msc()
+    msc = H.msc
+    masks = np.asarray(msc['masks'], dtype=np.int64)
+    signs = np.asarray(msc['signs'], dtype=np.int64)
+    if not masks.any():
+        return 'diagonal', None, 0j
+    one_bit = lambda v: (v & (v - 1)) == 0                    # (0 counts)
+    if not (one_bit(masks).all() and one_bit(signs).all() and np.all((masks == 0) | (signs == 0) | (signs == masks))):
+        return None, None, 0j
+    a = np.zeros((H.L, 3), dtype=np.complex128)
+    c0 = 0j
+    for mask, sign, coeff in zip(masks.tolist(), signs.tolist(), np.asarray(msc['coeffs']).tolist()):
+        if mask == 0 and sign == 0:
+            c0 += coeff
+        elif mask == 0:
+            a[sign.bit_length() - 1, 2] += coeff              # sigmaz_j = (0, 1 << j, 1)
+        elif sign == 0:
+            a[mask.bit_length() - 1, 0] += coeff              # sigmax_j = (1 << j, 0, 1)
+        else:
+            a[mask.bit_length() - 1, 1] += coeff / 1j         # sigmay_j = (1 << j, 1 << j, i)
+    return 'single-site', a, c0
+
+
+def site_exponentials(a, t):
+    """U_j = exp(-i t h_j) for h_j = a_j . sigma, the fields ``a`` an array (L, 3) and ``t`` real or complex: complex
+    array (L, 2, 2) of cos(t |a|) - i sin(t |a|) (a . sigma) / |a|, with |a| = sqrt(a . a) -- the norm of real fields;
+    |a| = 0 gives the identity exactly (for complex fields with a . a = 0, 1 - i t a . sigma)."""
+    a = np.asarray(a, dtype=np.complex128).reshape(-1, 3)
+    t = complex(t)
+    out = np.empty((a.shape[0], 2, 2), dtype=np.complex128)
+    for j, (ax, ay, az) in enumerate(a):
+        if ax == 0 and ay == 0 and az == 0:
+            out[j] = np.eye(2)
+            continue
+        if ax.imag == 0 and ay.imag == 0 and az.imag == 0:
+            th = float(np.sqrt(ax.real ** 2 + ay.real ** 2 + az.real ** 2))
+        else:
+            th = np.sqrt(ax * ax + ay * ay + az * az)
+        if th == 0:
+            c, s_over = 1.0, t                                # sin(t th) / th -> t
+        elif t.imag == 0 and np.imag(th) == 0:
+            c, s_over = np.cos(t.real * th), np.sin(t.real * th) / th
+        else:
+            c, s_over = np.cos(t * th), np.sin(t * th) / th
+        out[j] = [[c - 1j * s_over * az, -1j * s_over * (ax - 1j * ay)],
+                  [-1j * s_over * (ax + 1j * ay), c + 1j * s_over * az]]
+    return out
+
+
+_EXACT_STATS = {'reason': _lib.CONVERGED_TOL, 'its': 0, 'matvecs': 0, 'err_est': 0.0}
+
+
+def _evolve_exact(H, state, t, result):
+    """``algo='exact'`` (not in the reference): exp(-iHt) of a diagonal operator -- an element-wise phase, on any subspace
+    (``backend.expm_diagonal``) -- or of a sum of single-site operators -- a product of single-site rotations on the Full
+    space (``backend.site_ops_apply``) -- in one to four streaming passes, with no multiply and no tolerance; ``t`` may
+    be complex.  Anything else raises ``ValueError``."""
+    from . import backend
+    from .subspaces import Full
+    kind, a, c0 = product_operator_fields(H)
+    if kind is None:
+        raise ValueError("algo='exact' serves two classes of operators: diagonal ones (functions of the sigma-z alone) and "
+                         "sums of single-site operators plus a constant; this operator is neither (kicks alternate the "
+                         "two: evolve each factor on its own)")
+    sp = state.subspace
+    if kind == 'diagonal':
+        mat = H.get_mat(subspaces=(sp, sp))
+        if mat.nranks > 1:
+            raise NotImplementedError("algo='exact' on a partitioned state")
+        xin, yout = _adopt(mat, state, result)
+        backend.expm_diagonal(mat, xin, yout, -1j * complex(t))
+    else:
+        if type(sp) is not Full:
+            raise ValueError("algo='exact' with an operator that flips spins needs a state on the Full space, not %r "
+                             "(single-site rotations leave every other subspace)" % (sp,))
+        mats = site_exponentials(a, t)
+        if c0 != 0:
+            # the constant: a phase on the first site that is rotated at all
+            live = np.flatnonzero(np.any(a != 0, axis=1))
+            mats[int(live[0]) if live.size else 0] *= np.exp(-1j * complex(t) * c0)
+        backend.site_ops_apply(state.vec, sp._to_c(), mats, result.vec)
+    evolve.last_stats = dict(_EXACT_STATS)
+    evolve.last_mat = None
     result.set_initialized()
     return result
 
@@ -675,8 +772,113 @@ def _basis_weights_subspace(state, what):
     return sp, flip_sector
 
 
-def sample(state, shots, seed=None):
-    """``shots`` measurements of ``state`` in the computational basis: int64 array of product states as integers (bit
+def apply_site_operators(state, mats, sites=None, result=None):
+    """(x)_j M_j |state>: a product of single-site operators on a Full-space state, in place when ``result`` is
+    ``state``, into a new State when it is None.  ``mats`` is one 2 x 2 matrix for every spin of ``sites`` (all spins
+    when ``sites`` is None) or an array (n, 2, 2) with ``mats[i]`` for spin ``sites[i]``; the other spins get the
+    identity.  M acts on spin j with bit 0 = up, as everywhere here: (M psi)(.. c'_j ..) = sum_c M[c'_j][c_j] psi(.. c_j
+    ..); nothing requires M to be unitary.  One to four streaming passes on the device (``backend.site_ops_apply``).
+    A product of single-site operators leaves every symmetry sector: a Parity, SpinConserve or Explicit state is expanded
+    first, ``identity()`` with ``add_subspace(Full(), subspace)`` applied to it, an XParity state with
+    ``subspace.convert_state``; these raise ``ValueError``.  On more than one rank: ``NotImplementedError``."""
+    from . import backend
+    from .states import State
+    from .subspaces import Full, XParity
+    state.assert_initialized()
+    config._initialize()
+    sp = state.subspace
+    if type(sp) is XParity:
+        raise ValueError('site operators leave an XParity sector: expand with `convert_state` first (to the parent, and '
+                         'from there to Full)')
+    if type(sp) is not Full:
+        raise ValueError('site operators act on the Full space, not on %r: expand the state first -- op = identity(); '
+                         'op.add_subspace(Full(), state.subspace); op.dot(state)' % (sp,))
+    L = sp.L
+    mats = np.asarray(mats, dtype=np.complex128)
+    where = np.arange(L) if sites is None else np.asarray(sites).reshape(-1)
+    if where.size and (not np.issubdtype(where.dtype, np.integer) or where.min() < 0 or where.max() >= L
+                       or np.unique(where).size != where.size):
+        raise ValueError('sites must be distinct integers in [0, %d)' % L)
+    if mats.shape == (2, 2):
+        mats = np.broadcast_to(mats, (where.size, 2, 2))
+    if mats.shape != (where.size, 2, 2):
+        raise ValueError('site operators for %d sites are one (2, 2) matrix or an array (%d, 2, 2), not of shape %r'
+                         % (where.size, where.size, mats.shape))
+    full = np.broadcast_to(np.eye(2, dtype=np.complex128), (L, 2, 2)).copy()
+    full[where] = mats
+    if result is None:
+        result = State(L=L, subspace=sp)
+    elif result.subspace != sp:
+        raise ValueError('subspace of state and result must match')
+    backend.site_ops_apply(state.vec, sp._to_c(), full, result.vec)
+    result.set_initialized()
+    return result
+
+
+_SQRT_HALF = 1.0 / np.sqrt(2.0)
+# the rotation that takes the +1 eigenvector of a Pauli matrix to |0> (up) and the -1 eigenvector to |1>
+_BASIS_ROTATIONS = {'x': _SQRT_HALF * np.array([[1, 1], [1, -1]], dtype=np.complex128),
+                    'y': _SQRT_HALF * np.array([[1, -1j], [1, 1j]], dtype=np.complex128),
+                    'z': np.eye(2, dtype=np.complex128)}
+
+
+def basis_rotations(bases, L):
+    """The rotations (L, 2, 2) that precede a sigma-z measurement for ``bases``: a string of ``x`` / ``y`` / ``z`` of
+    length 1 (every spin) or L (character i for spin i), or an array (L, 2, 2) of unitaries of the caller's."""
+    if isinstance(bases, str):
+        if len(bases) not in (1, L) or set(bases.lower()) - set('xyz'):
+            raise ValueError("bases is a string of 'x', 'y', 'z' of length 1 or %d, not %r" % (L, bases))
+        chars = bases.lower() * L if len(bases) == 1 and L != 1 else bases.lower()
+        return np.array([_BASIS_ROTATIONS[ch] for ch in chars])
+    mats = np.asarray(bases, dtype=np.complex128)
+    if mats.shape != (L, 2, 2):
+        raise ValueError('bases is a string or an array of shape (%d, 2, 2), not %r' % (L, mats.shape))
+    if not np.allclose(np.einsum('jab,jcb->jac', mats, mats.conj()), np.eye(2), rtol=0, atol=1e-8):
+        raise ValueError('bases: every matrix must be unitary')
+    return mats
+
+
+def _rotated_copy(state, mats):
+    """A Full-space copy of ``state`` with the single-site rotations ``mats`` applied (for sampling in another basis)."""
+    import torch
+    from .operators import identity
+    from .states import State
+    from .subspaces import Full, XParity
+    sp = state.subspace
+    if type(sp) is XParity:
+        raise ValueError('sampling in another basis leaves an XParity sector: expand with `convert_state` first')
+    if not sp.product_state_basis:
+        raise ValueError('sampling in another basis needs a product state basis, not %r' % (sp,))
+    if config.world_size > 1:
+        raise NotImplementedError('sampling a partitioned state in another basis')
+    need = 16 << sp.L
+    free, _ = torch.cuda.mem_get_info()
+    if free < need:
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info()
+    if free < need:
+        raise MemoryError('sampling in another basis rotates a Full-space copy of the state: %d bytes, %d free on the '
+                          'device' % (need, free))
+    if type(sp) is Full:
+        work = state.copy()
+    else:
+        expand = identity()
+        expand.L = sp.L
+        expand.add_subspace(Full(L=sp.L), sp)
+        work = expand.dot(state)
+    return apply_site_operators(work, mats, result=work)
+
+
+def sample(state, shots, seed=None, bases=None):
+    """``shots`` measurements of ``state``: int64 array of outcomes as integers (bit i = spin i).  ``bases`` = None
+    measures every spin in the computational (sigma-z) basis, as described below.  Otherwise ``bases`` is a string of
+    ``x`` / ``y`` / ``z`` of length 1 or L, or an array (L, 2, 2) of unitaries applied before a sigma-z measurement:
+    bit i of an outcome set means eigenvalue -1 of the Pauli matrix measured on spin i (bit 0 is up, as everywhere
+    here).  A Full-space copy of the state is rotated on the device (``apply_site_operators``) and sampled; Parity,
+    SpinConserve and Explicit states are expanded first (16 * 2^L bytes must be free), XParity raises ``ValueError``.
+    All-``z`` bases take the path of ``bases=None``.
+
+    Computational basis: product states as integers (bit
     i = spin i, as ``subspace.idx_to_state`` gives them), drawn with probability |psi_c|^2 / <psi|psi> on the device
     (``backend.born_sample``: one pass over the state and a search per shot; the state is not copied to the host and
     need not be normalised).  A configuration of weight zero is never returned.  ``seed`` (an integer; None draws one
@@ -693,6 +895,10 @@ def sample(state, shots, seed=None):
     if seed is None:
         import os
         seed = int.from_bytes(os.urandom(8), 'little')
+    if bases is not None:
+        mats = basis_rotations(bases, sp.L)
+        if not np.array_equal(mats, np.broadcast_to(np.eye(2), mats.shape)):
+            return sample(_rotated_copy(state, mats), shots, seed=seed)
     # (an XParity descriptor is its parent's: the vector holds the parent's first dim / 2 rows)
     rows, flips = backend.born_sample(state.vec, sp._to_c(), shots, seed)
     if np.any(rows < 0):

@@ -264,10 +264,17 @@ class State:
         from . import computations
         return computations.sigmaz_correlations(self, connected=connected)
 
-    def sample(self, shots, seed=None):
-        """``shots`` measurements in the computational basis, drawn on the device -> computations.sample."""
+    def sample(self, shots, seed=None, bases=None):
+        """``shots`` measurements in the computational basis, or in the per-site bases ``bases``, drawn on the device
+        -> computations.sample."""
         from . import computations
-        return computations.sample(self, shots, seed=seed)
+        return computations.sample(self, shots, seed=seed, bases=bases)
+
+    def apply_site_operators(self, mats, sites=None, result=None):
+        """The product of the single-site operators ``mats`` on ``sites`` applied to this state (``result=self``: in
+        place) -> computations.apply_site_operators."""
+        from . import computations
+        return computations.apply_site_operators(self, mats, sites=sites, result=result)
 
     def participation_entropies(self, qs=(2,)):
         """The participation (basis Renyi) entropies S_q in one pass -> computations.participation_entropies."""

@@ -442,6 +442,31 @@ int dnm_perm_apply(const void *x, void *y, const dnm_subspace *sub, int xparity_
                    const double *coef, int accumulate, void *stream);
 int dnm_perm_dots(const void *phi, const void *psi, const dnm_subspace *sub, int xparity_sector, int nperm,
                   const int32_t *perms, double *out, void *stream);
+/* A product of single-site operators on a state, U = (x)_j M_j with M_j any 2 x 2 complex matrix on spin j -- global and
+ * per-site rotations, pulses, a change of the measurement basis (no counterpart in the reference, whose users evolve
+ * under a field or take the state to the host).  With spin j = index bit j,
+ *   y(c') = sum_c prod_j M_j[c'_j][c_j] x(c).
+ * mats_host: HOST, L matrices of 8 doubles, row-major, M[0][0], M[0][1], M[1][0], M[1][1] as (re, im) each; nothing
+ * requires them to be unitary.  x, y (device) are WHOLE Full-space states on one device, in index order or XOR-swizzled,
+ * read and written as they lie (the swizzle leaves the 4 low index bits alone, so 256-byte runs survive).  x == y is
+ * allowed: a tile is read whole before it is written.
+ * Sites are classed by bitwise comparison: the identity is skipped (site_pass -1); a diagonal matrix (M[0][1] = M[1][0] =
+ * 0) is a factor per row in the first pass and needs no tile bit (-2); every other site is general and belongs to one
+ * pass (site_pass = its index).  A pass stages tiles of tile_bits index bits in LDS -- the 4 low bits and tile_bits - 4
+ * others, chosen freely -- applies the butterflies of its sites and writes the tile back: every amplitude is read once and
+ * written once per pass.  General sites below bit 4 go into pass 0, the n_hi others fill the passes in ascending order:
+ * npasses = max(1, ceil(n_hi / (tile_bits - 4))); with L < tile_bits the tile is the whole vector.  All-identity input
+ * copies x to y, or returns at once when x == y.  No atomics, the grid follows from L and the plan alone, every index
+ * is 64-bit: two calls return the same bits.  The calls are asynchronous on the stream.
+ * Refused, each before any device call: null pointers, a subspace other than Full, a non-null site_perm, L outside
+ * [1, 62], a swizzle shift outside {0} and [5, 24], a matrix entry that is not finite.
+ * Cost: one read and one write of the vector per pass.
+ * dnm_site_ops_plan (host only, no device needed): tile_bits, the passes, site_pass (L entries), the workgroups of a
+ * pass -- min(2^(L - tile_bits), 2^16), at least one -- and the bytes of LDS of a launch, 16 << min(tile_bits, L); any
+ * output may be null. */
+int dnm_site_ops_plan(const dnm_subspace *sub, const double *mats_host, int *tile_bits, int *npasses, int8_t *site_pass,
+                      int *nworkgroups, size_t *lds_bytes);
+int dnm_site_ops_apply(const void *x, void *y, const dnm_subspace *sub, const double *mats_host, void *stream);
 /* The Gram matrix of many vectors in one pass over them (no counterpart in the reference, whose users take the overlaps
  * of a set of eigenvectors one State.dot at a time): for 1 <= nvec <= 64 device vectors of n complex128 elements each
  *   G[a][b] = sum_r conj(x_a[r]) x_b[r]      (nvec x nvec complex128, row-major, Hermitian),
@@ -476,6 +501,18 @@ int dnm_mat_sizes(const dnm_mat *A, int64_t *M, int64_t *N, int64_t *m_local, in
 int dnm_mat_precompute_diagonal(dnm_mat *A, void *stream);
 /* copies the cached diagonal (double[m_local]) to the host; error if absent */
 int dnm_mat_get_diagonal(dnm_mat *A, double *diag_host, void *stream);
+/* The exponential of a diagonal operator on a state, exact in one streaming pass (no counterpart in the reference, whose
+ * users call evolve):
+ *   y[p] = exp((s_re + i s_im) d_r) x[p],
+ * d_r the handle's diagonal at row r and p the position of r in the layout the handle multiplies in: a swizzled Full /
+ * Parity vector is indexed by position and the cached diagonal by row, in the SpinConserve internal layout the cache
+ * lies as the vectors do; Explicit and XParity handles work as far as dnm_mat_precompute_diagonal does, which the call
+ * runs itself when the handle has no cache.  exp and sincos in fp64.  Where x[p] is exactly 0, y[p] is 0, whatever exp
+ * gives for that row (padding, an overflowing exp(s_re d)); s = 0 copies x bit for bit.  x == y is allowed.
+ * Refused: null pointers, a host-only handle, a factor that is not finite, a handle with a non-zero mask ("operator is
+ * not diagonal"), a real-packed handle, more than one rank, different subspaces on the two sides.
+ * Cost: one read of x, 8 bytes per row of the cache and one write.  Asynchronous on the stream. */
+int dnm_mat_expm_diagonal(dnm_mat *A, const void *x, void *y, double s_re, double s_im, void *stream);
 /* MATOP_MULT -> MatMult_GPU (bcuda_template_2.cu:141-198): y = A x, y overwritten.
  * Single device (or a partition whose operator has no off-rank masks). */
 int dnm_mat_mult(dnm_mat *A, const void *x, void *y, void *stream);
