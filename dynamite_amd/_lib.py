@@ -167,6 +167,13 @@ SIGNATURES = {
     "dnm_perm_apply": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, C.c_int,
                                  vp]),
     "dnm_perm_dots": (C.c_int, [vp, vp, C.POINTER(Subspace), C.c_int, C.c_int, C.POINTER(C.c_int32), f64p, vp]),
+    "dnm_subspace_map_plan": (C.c_int, [C.POINTER(Subspace), C.c_int, C.POINTER(Subspace), C.c_int, i64p, i64p,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "dnm_subspace_map_indices": (C.c_int, [C.POINTER(Subspace), C.c_int, C.POINTER(Subspace), C.c_int, C.c_int64, i64p,
+                                           i64p, C.POINTER(C.c_int8), f64p]),
+    "dnm_subspace_map_apply": (C.c_int, [vp, C.POINTER(Subspace), C.c_int, vp, C.POINTER(Subspace), C.c_int, vp]),
+    "dnm_sector_weights_plan": (C.c_int, [C.POINTER(Subspace), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "dnm_sector_weights": (C.c_int, [vp, C.POINTER(Subspace), C.c_int, f64p, f64p, vp]),
     "dnm_site_ops_plan": (C.c_int, [C.POINTER(Subspace), f64p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_int8), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "dnm_site_ops_apply": (C.c_int, [vp, vp, C.POINTER(Subspace), f64p, vp]),

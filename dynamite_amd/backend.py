@@ -2209,6 +2209,118 @@ def perm_dots(phi, psi, subspace, perms, xparity_sector=0):
     return out
 
 
+def subspace_map_plan(sub_c, result_c, xparity_sector=0, result_xparity_sector=0):
+    """``dnm_subspace_map_plan`` (host only): (elements of the source vector, elements of the target vector, adjacent
+    target rows a thread owns, workgroups, bytes of LDS of a launch) of the map of a state from the subspace ``sub_c``
+    to ``result_c`` -- with a sector +-1, from or to the XParity sector over that descriptor."""
+    sr, dr, run, nw, lb = C.c_int64(), C.c_int64(), C.c_int(), C.c_int(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_subspace_map_plan(C.byref(sub_c), int(xparity_sector), C.byref(result_c),
+                                                int(result_xparity_sector), C.byref(sr), C.byref(dr), C.byref(run),
+                                                C.byref(nw), C.byref(lb)))
+    return sr.value, dr.value, run.value, nw.value, int(lb.value)
+
+
+def subspace_map_indices(sub_c, result_c, rows, xparity_sector=0, result_xparity_sector=0):
+    """``dnm_subspace_map_indices`` (host only): ``(idx, sign, scale)`` -- int64 and int8 arrays (len(rows), 2) and a
+    float -- for the target positions ``rows`` (in the vector as it lies), the positions in the source vector (as it
+    lies) of the at most two amplitudes that enter (-1: none), their signs (0: none) and the scale of the call, 1.0 or
+    0.70710678118654752440: ``y[r] = scale * sum sign * x[idx]``."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    idx = np.empty((rows.size, 2), dtype=np.int64)
+    sign = np.empty((rows.size, 2), dtype=np.int8)
+    scale = C.c_double()
+    _lib.check(_lib.lib().dnm_subspace_map_indices(C.byref(sub_c), int(xparity_sector), C.byref(result_c),
+                                                   int(result_xparity_sector), rows.size, _lib.p64(rows), _lib.p64(idx),
+                                                   sign.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(scale)))
+    return idx, sign, scale.value
+
+
+def _as_it_lies(vec, sub_c):
+    """``(device tensor, descriptor)`` of a vector for the subspace maps: a SpinConserve vector in the internal layout in
+    reference order (one extra vector), every other as it lies, under a descriptor that names the vector's layout."""
+    x, d = _reference_order(vec, sub_c)
+    swz = 0 if vec.internal else vec.swz
+    if int(d.vec_swizzle) != swz:
+        d = _lib.Subspace.from_buffer_copy(d)
+        d.vec_swizzle = swz
+        d.site_perm = None               # (a relabelling belongs to the internal layout, which this vector is not in)
+        d._parent_desc = sub_c           # (the copy points into the tables of the original)
+    return x, d
+
+
+def subspace_map(vec, subspace, result, result_subspace, xparity_sector=0, result_xparity_sector=0):
+    """``result`` = the state ``vec`` moved from its subspace to another of the same spins (``dnm_subspace_map_apply``,
+    one gather pass over the target): the orthogonal projection of the state onto the span of the target subspace -- an
+    embedding, a restriction, or the way into or out of an XParity sector; nothing is normalised.  ``subspace`` and
+    ``result_subspace`` are the descriptors (``_to_c()``) of the Full, Parity, SpinConserve or Explicit subspaces of the
+    two vectors -- with a sector +-1 that of the parent of the XParity subspace whose representatives the vector holds.
+    Swizzled Full / Parity vectors are read and written as they lie, each in its own layout; a SpinConserve vector in
+    the internal layout is converted to reference order first and the result is written in reference order to a scratch
+    vector and brought home (one extra vector each).  On more than one rank this raises ``NotImplementedError``."""
+    import torch
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('%s of a partitioned state: the source amplitudes of a rank\'s rows lie on other '
+                                  'ranks' % 'subspace maps')
+    if result is vec:
+        raise ValueError('subspace maps: the result must be another vector than the state (the pass gathers)')
+    s_c, r_c = subspace['data'], result_subspace['data']
+    x, sd = _as_it_lies(vec, s_c)
+    if result.internal:
+        y = torch.empty(result.rows, dtype=x.dtype, device=x.device)
+        rd = _lib.Subspace.from_buffer_copy(r_c)
+        rd.vec_swizzle = 0
+        rd.site_perm = None
+    else:
+        y = result.array
+        rd = r_c
+        if int(rd.vec_swizzle) != result.swz:
+            rd = _lib.Subspace.from_buffer_copy(r_c)
+            rd.vec_swizzle = result.swz
+            rd.site_perm = None
+    nx, ny = subspace_map_plan(sd, rd, xparity_sector, result_xparity_sector)[:2]
+    if x.numel() != nx or y.numel() != ny:
+        raise ValueError('subspace maps: vectors of %d and %d amplitudes for subspaces of %d and %d'
+                         % (x.numel(), y.numel(), nx, ny))
+    _lib.check(_lib.lib().dnm_subspace_map_apply(C.c_void_p(x.data_ptr()), C.byref(sd), int(xparity_sector),
+                                                 C.c_void_p(y.data_ptr()), C.byref(rd), int(result_xparity_sector),
+                                                 _stream()))
+    if result.internal:
+        result.set_local_natural(y)
+    return result
+
+
+def sector_weights_plan(sub_c, xparity_sector=0):
+    """``dnm_sector_weights_plan`` (host only): (workgroups, bytes of scratch) of the sector-weights pass."""
+    nw, sb = C.c_int(), C.c_size_t()
+    _lib.check(_lib.lib().dnm_sector_weights_plan(C.byref(sub_c), int(xparity_sector), C.byref(nw), C.byref(sb)))
+    return nw.value, int(sb.value)
+
+
+def sector_weights(vec, subspace, xparity_sector=0, flip=True):
+    """``(magnetization, flip)`` of a state from one streaming pass over it (``dnm_sector_weights``): the L + 1 sums of
+    |psi(c)|^2 over the configurations with k set bits, and (F+, F-), the squared norms the two XParity sectors keep --
+    ``None`` when ``flip`` is false.  Raw sums, nothing normalised; two calls return the same bits.  ``subspace`` and
+    ``xparity_sector`` as for ``subspace_map``; the flip sums are refused on Explicit subspaces and on subspaces that
+    cannot carry the flip.  On more than one rank this raises ``NotImplementedError``."""
+    config._initialize()
+    if _dist() is not None:
+        raise NotImplementedError('%s of a partitioned state: the source amplitudes of a rank\'s rows lie on other '
+                                  'ranks' % 'sector weights')
+    sub_c = subspace['data']
+    x, d = _as_it_lies(vec, sub_c)
+    full = C.c_int64()
+    _lib.check(_lib.lib().dnm_subspace_dim(C.byref(d), C.byref(full)))
+    expect = full.value // 2 if xparity_sector else full.value
+    if x.numel() != expect:
+        raise ValueError('a state of %d amplitudes on a subspace of %d' % (x.numel(), expect))
+    mag = np.empty(int(d.L) + 1, dtype=np.float64)
+    fl = np.empty(2, dtype=np.float64) if flip else None
+    _lib.check(_lib.lib().dnm_sector_weights(C.c_void_p(x.data_ptr()), C.byref(d), int(xparity_sector), _lib.pf64(mag),
+                                             _lib.pf64(fl) if flip else None, _stream()))
+    return mag, fl
+
+
 def _pauli_cols_c(cols):
     cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, 2)
     return cols, cols.ctypes.data_as(C.POINTER(C.c_int32))

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdynamite_amd.so")
-SOURCES = ["matvec_kernels.hip", "row_fused_kernels.hip", "sc3_kernels.hip", "sc3g_kernels.hip", "vec_kernels.hip", "rdm_kernels.hip", "rdm_sector_kernels.hip", "zz_kernels.hip", "pm_kernels.hip", "swap_kernels.hip", "cyc_kernels.hip", "perm_kernels.hip", "pauli_kernels.hip", "vgram_kernels.hip", "born_kernels.hip", "site_ops_kernels.hip", "plan.cpp", "sc3_perm.cpp", "sc3_tables.cpp", "passes.cpp", "mat.cpp", "mat_mult.cpp", "observables.cpp", "site_ops.cpp", "vec_api.cpp", "krylov_host.cpp", "krylov.cpp", "comm.cpp"]
+SOURCES = ["matvec_kernels.hip", "row_fused_kernels.hip", "sc3_kernels.hip", "sc3g_kernels.hip", "vec_kernels.hip", "rdm_kernels.hip", "rdm_sector_kernels.hip", "zz_kernels.hip", "pm_kernels.hip", "swap_kernels.hip", "cyc_kernels.hip", "perm_kernels.hip", "submap_kernels.hip", "pauli_kernels.hip", "vgram_kernels.hip", "born_kernels.hip", "site_ops_kernels.hip", "plan.cpp", "sc3_perm.cpp", "sc3_tables.cpp", "passes.cpp", "mat.cpp", "mat_mult.cpp", "observables.cpp", "site_ops.cpp", "vec_api.cpp", "krylov_host.cpp", "krylov.cpp", "comm.cpp"]
 ARCH = "gfx950"
 # tile_pass_kernel sits at the 128-VGPR edge of 4 waves per SIMD; these two scheduler options of the AMDGPU backend
 # measured -2.1 % on the L=30 multiply, same box (profiles/r02_exp22_sched.txt; max-ilp / iterative-minreg: +12...17 %);

@@ -780,7 +780,8 @@ def apply_site_operators(state, mats, sites=None, result=None):
     ..); nothing requires M to be unitary.  One to four streaming passes on the device (``backend.site_ops_apply``).
     A product of single-site operators leaves every symmetry sector: a Parity, SpinConserve or Explicit state is expanded
     first, ``identity()`` with ``add_subspace(Full(), subspace)`` applied to it, an XParity state with
-    ``subspace.convert_state``; these raise ``ValueError``.  On more than one rank: ``NotImplementedError``."""
+    ``subspace.convert_state`` -- or either, on the device, with ``state.to_subspace(Full())``; these raise
+    ``ValueError``.  On more than one rank: ``NotImplementedError``."""
     from . import backend
     from .states import State
     from .subspaces import Full, XParity
@@ -1521,6 +1522,77 @@ def symmetry_representation(states, perms):
         for n in range(N):
             D[:, m, n] = symmetry_expectations(states[n], perms, other=states[m])
     return D
+
+
+def _map_side(subspace, what):
+    """(subspace whose ``_to_c()`` the subspace maps take, XParity sector or 0): Full, Parity, SpinConserve, Explicit
+    and Auto, and XParity over those (the descriptor is then the parent's)."""
+    from .subspaces import Explicit, Full, Parity, SpinConserve, XParity
+    base, sector = (subspace.parent, int(subspace.sector)) if type(subspace) is XParity else (subspace, 0)
+    if not isinstance(base, (Full, Parity, SpinConserve, Explicit)):
+        raise ValueError('%s need a Full, Parity, SpinConserve, Explicit or Auto subspace, or XParity over one of them, '
+                         'not %r' % (what, subspace))
+    return subspace, sector
+
+
+def to_subspace(state, subspace, result=None):
+    """``state`` moved to ``subspace``, a subspace of the same spins, as a new ``State`` on it (or into ``result``, a
+    state on ``subspace``): the orthogonal projection, onto the span of ``subspace``, of the state seen as a vector of
+    the whole 2^L space -- an embedding when the configurations of the state's subspace lie in ``subspace`` (a
+    SpinConserve or XParity eigenvector taken to Full, where ``apply_site_operators``, ``sample(bases=...)`` and the
+    Pauli correlators accept it), a restriction the other way round.  One gather pass over the target on the device
+    (``backend.subspace_map``); nothing travels through the host.  It is not normalised: the squared norm of the result
+    is the weight of the state inside the target subspace, 1 for an embedding of a normalised state.  Full, Parity,
+    SpinConserve, Explicit and Auto on either side, and XParity over those (``XParity.convert_state`` does the two cases
+    sector <-> parent on the host and agrees to rounding: it divides by sqrt(2) where this pass multiplies by
+    0.70710678118654752440).  Between two plain subspaces and between two XParity sectors the result holds the bits of
+    the state.  One process; on more it raises ``NotImplementedError``."""
+    from . import backend
+    from .states import State
+    config._initialize()
+    state.assert_initialized()
+    what = 'subspace maps'
+    if subspace.L is None:
+        subspace = subspace.copy()
+        subspace.L = state.L
+    if subspace.L != state.L:
+        raise ValueError('%s: a state of %d spins and a subspace of %d' % (what, state.L, subspace.L))
+    src, ssec = _map_side(state.subspace, what)
+    dst, dsec = _map_side(subspace, what)
+    if result is state:
+        raise ValueError('%s: the result must be another state than the input (the pass gathers)' % what)
+    if result is None:
+        result = State(L=state.L, subspace=subspace)
+    elif result.subspace != subspace:
+        raise ValueError('subspace of result must be the target subspace')
+    backend.subspace_map(state.vec, src._to_c(), result.vec, result.subspace._to_c(), ssec, dsec)
+    result.set_initialized()
+    return result
+
+
+def sector_weights(state):
+    """``(magnetization, flip)`` of a state from one streaming pass over it on the device
+    (``backend.sector_weights``).  ``magnetization``: array of L + 1 numbers, entry k the sum of |psi(c)|^2 over the
+    configurations c with k set bits -- the full counting statistics of the magnetisation, and the squared norm
+    ``to_subspace(SpinConserve(L, k))`` keeps.  ``flip``: array (F+, F-), the squared norms the two sectors of the global
+    spin flip keep (``to_subspace(XParity(..., '+'))`` and ``'-'``), or ``None`` where the flip is not defined: on
+    Explicit and Auto subspaces, Parity with odd L and SpinConserve away from half filling.  Neither is normalised; two
+    calls return the same bits.  Subspaces as for ``to_subspace``; one process."""
+    from . import backend
+    from .subspaces import Explicit
+    config._initialize()
+    state.assert_initialized()
+    sp, sector = _map_side(state.subspace, 'sector weights')
+    base = sp.parent if sector else sp
+    has_flip = bool(sector) or (not isinstance(base, Explicit) and _carries_flip(base))
+    return backend.sector_weights(state.vec, sp._to_c(), sector, flip=has_flip)
+
+
+def _carries_flip(subspace):
+    """Does a Full, Parity or SpinConserve subspace carry the global spin flip (its rows i and dim - 1 - i are then
+    complements of each other)?"""
+    from .subspaces import Full, XParity
+    return isinstance(subspace, Full) or XParity._flip_closed(subspace) is None
 
 
 def _entropy_of_spectrum(w):

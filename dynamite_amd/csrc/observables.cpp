@@ -1,7 +1,8 @@
 // C ABI: the observables of a state that are computed in one pass over it and never touch a shell matrix -- reduced
 // density matrices (dense and sector by sector) and the sigma-z, sigma+ sigma-, bond-swap, three-site rotation
 // (chirality) and two-spin Pauli moments -- the Gram matrix of many vectors, which runs on the same panel scheme, the
-// site permutations of a state (two plain gather kernels, no panel), and Born sampling with the power sums of the
+// site permutations of a state (two plain gather kernels, no panel), the maps of a state between subspaces with its
+// weights per sector (a gather and a streaming kernel, no panel), and Born sampling with the power sums of the
 // participation entropies (streaming passes over |x_i|^2, no panel).  They share the cached scratch of the partial
 // tiles.
 #include "born.h"
@@ -11,6 +12,7 @@
 #include "cyc_rank.h"
 #include "pauli_cols.h"
 #include "perm.h"
+#include "submap.h"
 #include "vgram.h"
 
 #include <algorithm>
@@ -862,6 +864,155 @@ int dnm_perm_dots(const void *phi, const void *psi, const dnm_subspace *sub, int
                            scratch, partial, o_dev, S(stream)));
   // (synchronises: the host tables and `big` are released on return)
   return dnm_memcpy_d2h(out, o_dev, obytes, stream);
+}
+
+// ---- subspace maps and sector weights (submap.h, submap_kernels.hip) -----------------------------------------------
+// one side of a map, or the subspace of the sector weights: what every entry point checks, before any device call
+static int submap_check_side(const dnm_subspace *sub, int xsec, const char *what, const char *side, SubView *v) {
+  DNM_CHECK(sub->type == DNM_FULL || sub->type == DNM_PARITY || sub->type == DNM_EXPLICIT ||
+            sub->type == DNM_SPIN_CONSERVE, "%s: unknown subspace type %d%s", what, sub->type, side);
+  DNM_CHECK(sub->L >= 1 && sub->L <= 63, "%s: L=%lld out of range%s (1 to 63 spins)", what, (long long)sub->L, side);
+  DNM_CHECK(sub->type != DNM_FULL || sub->L <= 62, "%s: 2^%lld rows%s (at most 62 index bits)", what, (long long)sub->L,
+            side);
+  DNM_CHECK(sub->site_perm == nullptr, "%s: no relabelled subspace%s (site_perm given): hand over the state in "
+            "reference order with a descriptor without it", what, side);
+  if (sub->type == DNM_SPIN_CONSERVE)
+    DNM_CHECK(sub->vec_swizzle == 0, "%s: a SpinConserve state is read and written in reference order%s (vec_swizzle %d "
+              "given: dnm_vec_layout_copy converts)", what, side, sub->vec_swizzle);
+  else if (sub->type == DNM_EXPLICIT)
+    DNM_CHECK(sub->vec_swizzle == 0, "%s: vec_swizzle %d on an Explicit subspace%s", what, sub->vec_swizzle, side);
+  else
+    DNM_CHECK(sub->vec_swizzle == 0 || (sub->vec_swizzle >= 5 && sub->vec_swizzle <= 24),
+              "%s: vec_swizzle %d%s: the shift of a swizzled vector lies in [5, 24]", what, sub->vec_swizzle, side);
+  DNM_CHECK(xsec == 0 || xsec == 1 || xsec == -1, "%s: xparity sector %d%s (0, +1 or -1)", what, xsec, side);
+  DNM_TRY(view_from_c(sub, v));
+  if (xsec != 0) {
+    if (sub->type == DNM_PARITY)
+      DNM_CHECK(sub->L % 2 == 0, "%s: Parity carries the global flip of XParity only when L is even (L=%lld)%s", what,
+                (long long)sub->L, side);
+    if (sub->type == DNM_SPIN_CONSERVE)
+      DNM_CHECK(sub->L == 2 * sub->k, "%s: SpinConserve carries the global flip of XParity only when k = L / 2 "
+                "(L=%lld, k=%lld)%s", what, (long long)sub->L, (long long)sub->k, side);
+    if (sub->type == DNM_EXPLICIT) {
+      DNM_CHECK(sub->dim % 2 == 0, "%s: an Explicit subspace of odd dimension %lld carries no XParity sector%s", what,
+                (long long)sub->dim, side);
+      // (the whole closure check is XParity's constructor's; here: the halves meet where they should)
+      const int64_t h = sub->dim / 2;
+      DNM_CHECK(((sub->state_map[h - 1] >> (sub->L - 1)) & 1) == 0 && ((sub->state_map[h] >> (sub->L - 1)) & 1) == 1,
+                "%s: an XParity sector over an Explicit subspace needs the representatives (spin L-1 up) in the first "
+                "half of the list and their complements in the second%s", what, side);
+    }
+  }
+  return 0;
+}
+
+static int submap_check(const dnm_subspace *src, int src_sector, const dnm_subspace *dst, int dst_sector, SubView *sv,
+                        SubView *dv) {
+  const char *what = "subspace map";
+  DNM_CHECK(src && dst, "%s: null subspace descriptor", what);
+  DNM_TRY(submap_check_side(src, src_sector, what, " (source)", sv));
+  DNM_TRY(submap_check_side(dst, dst_sector, what, " (target)", dv));
+  DNM_CHECK(src->L == dst->L, "%s: the source has L=%lld spins, the target L=%lld", what, (long long)src->L,
+            (long long)dst->L);
+  return 0;
+}
+
+int dnm_subspace_map_plan(const dnm_subspace *src, int src_sector, const dnm_subspace *dst, int dst_sector,
+                          int64_t *src_rows, int64_t *dst_rows, int *run, int *nworkgroups, size_t *lds_bytes) {
+  SubView sv{}, dv{};
+  DNM_TRY(submap_check(src, src_sector, dst, dst_sector, &sv, &dv));
+  SubmapPlan p;
+  DNM_TRY(submap_plan(sv, src_sector, dv, dst_sector, &p));
+  if (src_rows) *src_rows = p.src.rows;
+  if (dst_rows) *dst_rows = p.dst.rows;
+  if (run) *run = p.run;
+  if (nworkgroups) *nworkgroups = p.nwg;
+  if (lds_bytes) *lds_bytes = p.lds_bytes;
+  return 0;
+}
+
+int dnm_subspace_map_indices(const dnm_subspace *src, int src_sector, const dnm_subspace *dst, int dst_sector,
+                             int64_t n, const int64_t *rows, int64_t *idx, int8_t *sign, double *scale) {
+  SubView sv{}, dv{};
+  DNM_TRY(submap_check(src, src_sector, dst, dst_sector, &sv, &dv));
+  DNM_CHECK(n >= 0 && (n == 0 || (rows && idx && sign)), "subspace map indices: null argument");
+  SubOwned s, d;           // (host only: the bucket table of an Explicit side as the kernel has it)
+  DNM_TRY(s.init(src, false));
+  DNM_TRY(d.init(dst, false));
+  SubmapPlan p;
+  DNM_TRY(submap_plan(s.host, src_sector, d.host, dst_sector, &p));
+  if (scale) *scale = submap_scale(p.mode);
+  for (int64_t i = 0; i < n; ++i)
+    DNM_CHECK(rows[i] >= 0 && rows[i] < p.dst.rows, "subspace map indices: row %lld of %lld rows", (long long)rows[i],
+              (long long)p.dst.rows);
+  return submap_dispatch(sv.type, dv.type, [&](auto S, auto D) {
+    for (int64_t i = 0; i < n; ++i) {
+      SubmapTerms t;
+      submap_terms<decltype(S)::value>(submap_row_config<decltype(D)::value>(rows[i], p.dst.v), p.src, dst_sector, &t);
+      for (int m = 0; m < 2; ++m) {
+        idx[2 * i + m] = t.idx[m];
+        sign[2 * i + m] = (int8_t)t.sign[m];
+      }
+    }
+    return 0;
+  });
+}
+
+int dnm_subspace_map_apply(const void *x, const dnm_subspace *src, int src_sector, void *y, const dnm_subspace *dst,
+                           int dst_sector, void *stream) {
+  DNM_CHECK(x && y, "subspace map: null argument");
+  DNM_CHECK(x != y, "subspace map: x and y are the same vector (the pass gathers: the result needs its own)");
+  SubView sv{}, dv{};
+  DNM_TRY(submap_check(src, src_sector, dst, dst_sector, &sv, &dv));
+  SubOwned s, d;
+  DNM_TRY(s.init(src, true));
+  DNM_TRY(d.init(dst, true));
+  SubmapPlan p;
+  DNM_TRY(submap_plan(s.host, src_sector, d.host, dst_sector, &p));
+  p.src.v = s.dev;
+  p.dst.v = d.dev;
+  DNM_TRY(launch_submap(x, y, p, S(stream)));
+  DNM_HIP(hipStreamSynchronize(S(stream)));     // the subspace tables are released on return
+  return 0;
+}
+
+int dnm_sector_weights_plan(const dnm_subspace *sub, int xparity_sector, int *nworkgroups, size_t *scratch_bytes) {
+  DNM_CHECK(sub, "sector weights: null subspace descriptor");
+  SubView v{};
+  DNM_TRY(submap_check_side(sub, xparity_sector, "sector weights", "", &v));
+  SectorWeightsPlan p;
+  DNM_TRY(sector_weights_plan(v, xparity_sector, &p));
+  if (nworkgroups) *nworkgroups = p.nwg;
+  if (scratch_bytes) *scratch_bytes = p.partial_bytes + (size_t)p.ncols * sizeof(double);
+  return 0;
+}
+
+int dnm_sector_weights(const void *x, const dnm_subspace *sub, int xparity_sector, double *popcount_out,
+                       double *flip_out, void *stream) {
+  const char *what = "sector weights";
+  DNM_CHECK(x && sub && popcount_out, "%s: null argument", what);
+  SubView v{};
+  DNM_TRY(submap_check_side(sub, xparity_sector, what, "", &v));
+  SectorWeightsPlan p;
+  DNM_TRY(sector_weights_plan(v, xparity_sector, &p));
+  DNM_CHECK(!flip_out || xparity_sector != 0 || p.pairs, "%s: the sectors of the global flip are defined on Full, on "
+            "Parity with even L, on SpinConserve(L, L/2) and on XParity states, not on this subspace (type %d, L=%d): "
+            "pass a null flip_out", what, v.type, v.L);
+  SubOwned s;
+  DNM_TRY(s.init(sub, true));
+  p.side.v = s.dev;
+  const size_t obytes = (size_t)p.ncols * sizeof(double);
+  DevBuf big;
+  void *scratch = nullptr;       // the workgroups' partial sums, then the sums
+  DNM_TRY(rdm_scratch(p.partial_bytes + obytes, &big, &scratch, what, 0, 0, p.nwg));
+  void *o_dev = (char *)scratch + p.partial_bytes;
+  DNM_TRY(launch_sector_weights(x, p, scratch, o_dev, S(stream)));
+  std::vector<double> sums((size_t)p.ncols);
+  // (synchronises: the subspace tables and `big` are released on return)
+  DNM_TRY(dnm_memcpy_d2h(sums.data(), o_dev, obytes, stream));
+  memcpy(popcount_out, sums.data(), ((size_t)v.L + 1) * sizeof(double));
+  if (flip_out) memcpy(flip_out, sums.data() + v.L + 1, 2 * sizeof(double));
+  return 0;
 }
 
 // ---- Gram matrix of many vectors ----------------------------------------------------------------------------------

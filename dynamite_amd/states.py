@@ -349,6 +349,18 @@ class State:
         from . import computations
         return computations.symmetry_representation(states, perms)
 
+    def to_subspace(self, subspace, result=None):
+        """This state moved to ``subspace`` (embedded, restricted, into or out of an XParity sector) on the device, not
+        normalised: its squared norm is the weight of the state inside ``subspace`` -> computations.to_subspace."""
+        from . import computations
+        return computations.to_subspace(self, subspace, result=result)
+
+    def sector_weights(self):
+        """``(magnetization, flip)``: the weight of the state per number of set bits and per sector of the global spin
+        flip, from one pass -> computations.sector_weights."""
+        from . import computations
+        return computations.sector_weights(self)
+
     def entanglement_spectrum(self, keep):
         """Eigenvalues of the reduced density matrix on ``keep`` -> computations.entanglement_spectrum."""
         from . import computations

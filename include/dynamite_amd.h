@@ -442,6 +442,61 @@ int dnm_perm_apply(const void *x, void *y, const dnm_subspace *sub, int xparity_
                    const double *coef, int accumulate, void *stream);
 int dnm_perm_dots(const void *phi, const void *psi, const dnm_subspace *sub, int xparity_sector, int nperm,
                   const int32_t *perms, double *out, void *stream);
+/* A state moved from one subspace to another of the same L spins on the device -- embed, restrict, into and out of an
+ * XParity sector -- and its weight per sector (no counterpart in the reference, whose users take the state to the host;
+ * its XParity.convert_state does so too and knows only a sector and its parent).  The result of the map is the
+ * orthogonal projection, onto the span of the target subspace, of the source state seen as a vector of the whole 2^L
+ * space: an embedding when the source's configurations lie in the target's, a restriction the other way round.  Nothing
+ * is normalised: the squared norm of the result is the weight of the state inside the target.  With psi(c) the amplitude
+ * of configuration c in the source -- x[i_src(c)], or 0 when c is not in the source; for a source on the XParity sector
+ * s over a parent, kappa x[i(c)] for c in the parent with bit L - 1 clear and kappa s x[i(cbar)] with it set, cbar = c
+ * with all L spins flipped, kappa the double 0.70710678118654752440 -- and c the configuration of the target row r (the
+ * representative, bit L - 1 clear, when the target is an XParity sector t):
+ *   plain     -> plain       y[r] = x[i_src(c)] or 0                       the bits of x are copied
+ *   XParity s -> plain       y[r] = x[.] * kappa, the sign s on the flipped half, or 0     one multiply per component
+ *   plain     -> XParity t   y[r] = (psi(c) + t psi(cbar)) * kappa         one add, then one multiply per component
+ *   XParity s -> XParity t   y[r] = x[i(c)] if s == t and c lies in the source's parent, else 0     the bits are copied
+ * src_sector / dst_sector = +-1: that side's vector holds the dim / 2 amplitudes of the representatives of that XParity
+ * sector and the descriptor is the parent's (the convention of dnm_swap_moments); 0: the subspace itself.  Full, Parity,
+ * SpinConserve and Explicit on either side; an Explicit side is searched in its sorted or re-mapped table.
+ * x, y (device) are WHOLE states on one device, distinct (the pass gathers).  Layouts: Full / Parity in index order or
+ * XOR-swizzled, read and written as they lie, each side by its own descriptor's shift; SpinConserve in reference order
+ * (the caller converts: dnm_vec_layout_copy); Explicit in list order.  One target-driven kernel, no atomics; rows whose
+ * configuration is not in the source are written as zeros by the same store.  dnm_subspace_map_apply synchronises the
+ * stream.
+ * Refused, each before any device call: null pointers, x == y, different L on the two sides, L outside [1, 63] or more
+ * than 62 index bits, an unknown subspace type, a sector other than 0, +1, -1, an XParity parent that cannot carry the
+ * flip (Parity with odd L, SpinConserve with L != 2 k, Explicit with odd dimension or whose rows dim / 2 - 1 and dim / 2
+ * do not have bit L - 1 clear and set respectively), a non-null site_perm, the SpinConserve internal layout, a swizzle
+ * shift outside {0} and [5, 24].
+ * dnm_subspace_map_plan (host only, no device needed): the elements of the two vectors, the adjacent target rows a
+ * thread owns (4 for a SpinConserve target, which it unranks once and steps through; 1 otherwise), the workgroups of
+ * the launch -- ceil(target rows / 1024), at most 4096, at least one -- and the bytes of LDS of a launch (the binomials
+ * of the SpinConserve sides); any output may be null.
+ * dnm_subspace_map_indices (host only): for each of the n target positions rows[i] (in the vector as it lies), the
+ * positions idx[2 i], idx[2 i + 1] in the source vector (as it lies) of the at most two amplitudes that enter, -1 for a
+ * missing one, their signs sign[2 i], sign[2 i + 1] (0 for a missing one) and the one scale of the call, 1.0 or kappa:
+ * y[r] = scale * sum sign * x[idx].  The arithmetic is the kernel's (csrc/submap_rank.h).
+ * dnm_sector_weights: popcount_out[k] (HOST, L + 1 doubles) = sum of |psi(c)|^2 over the configurations with k set bits
+ * -- the counting statistics of the magnetisation, and the squared norm a map to SpinConserve(L, k) keeps; on an XParity
+ * state a representative row adds |x|^2 / 2 to bin k and as much to bin L - k.  flip_out (HOST, 2 doubles, may be null) =
+ * (F+, F-), F+- = sum over the pairs {c, cbar} of |psi(c) +- psi(cbar)|^2 / 2, the squared norm each XParity sector
+ * keeps: the pairs are the rows i and dim - 1 - i of Full, of Parity with even L and of SpinConserve(L, L / 2); on an
+ * XParity state the sector's entry is the squared norm and the other 0; a non-null flip_out is refused on Explicit and
+ * on subspaces that cannot carry the flip.  One streaming pass, no floating-point atomics, and the number of workgroups
+ * follows from the rows alone: two calls return the same bits.  Layouts and refusals as for the map; the call
+ * synchronises the stream like dnm_vec_dot, scratch comes from the library's workspace (dnm_release_workspace).
+ * dnm_sector_weights_plan (host only): the workgroups -- ceil(rows / 1024), rows counted in pairs where the flip sums
+ * come with the bins, at most 2048 -- and the bytes of scratch; any output may be null. */
+int dnm_subspace_map_plan(const dnm_subspace *src, int src_sector, const dnm_subspace *dst, int dst_sector,
+                          int64_t *src_rows, int64_t *dst_rows, int *run, int *nworkgroups, size_t *lds_bytes);
+int dnm_subspace_map_indices(const dnm_subspace *src, int src_sector, const dnm_subspace *dst, int dst_sector,
+                             int64_t n, const int64_t *rows, int64_t *idx, int8_t *sign, double *scale);
+int dnm_subspace_map_apply(const void *x, const dnm_subspace *src, int src_sector, void *y, const dnm_subspace *dst,
+                           int dst_sector, void *stream);
+int dnm_sector_weights_plan(const dnm_subspace *sub, int xparity_sector, int *nworkgroups, size_t *scratch_bytes);
+int dnm_sector_weights(const void *x, const dnm_subspace *sub, int xparity_sector, double *popcount_out,
+                       double *flip_out, void *stream);
 /* A product of single-site operators on a state, U = (x)_j M_j with M_j any 2 x 2 complex matrix on spin j -- global and
  * per-site rotations, pulses, a change of the measurement basis (no counterpart in the reference, whose users evolve
  * under a field or take the state to the host).  With spin j = index bit j,
